@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: decided consensus instances/sec at n=64, f=21 (BASELINE.json configs[3]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--instances I] [--legs reference,spec]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--instances I] [--dump-outputs DIR]
+    python bench.py --full [--legs reference,spec,...]                         (every leg + CPU baseline)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (multi-GPU)
+
+A plain run measures the headline only: it builds the engine of one leg (the reference leg, or the one
+--mode / --legs names), warms up, times --steps steps and prints the result line.  --full adds the other
+legs, the C-oracle CPU baseline and the recorded rate of the reference's own Python path.
+--dump-outputs DIR writes what the headline leg's last timed step computed (dump_outputs below) as
+DIR/<name>.npy; the workload is seeded, so two builds run with the same arguments compare array for array.
 
 Workload: 64 replicas, f = 21, adversarial delays (messages from/to a
 per-instance slow set of f replicas take D = 8 steps, all others 1), Philox Bernoulli(1/2)
@@ -12,7 +19,7 @@ reference's decide() upcall, core/byzantinerandomizedconsensus.py:94).  Instance
 independent, so ranks shard them (global Philox ids => results independent of N: weak
 scaling); the only collective is one RCCL all-reduce of the statistics.
 
-Legs, one JSON line (rank 0); each leg is one launch per step at 2^20 instances:
+Legs (--full runs them all), one JSON line (rank 0); each leg is one launch per step at 2^20 instances:
   reference  the protocol exactly as the reference runs it (quirks included) -- the headline
              `value`, on the step kernel (per-receiver cells: the general path).  Its coin branch is dead, so split proposals decide "-1" in
              round 1; `decided_value_hist` shows that share.
@@ -36,8 +43,8 @@ Legs, one JSON line (rank 0); each leg is one launch per step at 2^20 instances:
              this delay model only (the engine's default kernel for it, same results as the step kernel:
              tests/test_gpu_fullsize.py); the headline stays on the general step kernel.
   spec2c     the spec leg's workload on the same two-class form.
-The legs of seconds per step (many, long, spec64) time at most LEG_STEPS of --steps / --warmup
-and report the counts they timed.
+The headline leg times exactly --steps steps after --warmup warm-ups.  Beside it, the legs of seconds
+per step (many, long, spec64) time at most LEG_STEPS of them and report the counts they timed.
 """
 import argparse
 import json
@@ -70,8 +77,8 @@ LEGS = {"reference": ("reference", "sender", "slowset", DELAY_MAX, 4, "step"),
         "spec2c": ("spec", "sender", "slowset", DELAY_MAX, 8, "life")}
 # legs with a round cap of their own (the others take --round-cap)
 LEG_CAP = {"many": MANY_CAP, "long": LONG_CAP, "spec64": LONG_CAP}
-# legs of seconds per step time at most this many (steps, warmup) of --steps / --warmup, so that the default
-# run stays within minutes; every leg reports the steps it timed
+# legs of seconds per step time at most this many (steps, warmup) of --steps / --warmup beside the headline,
+# so that a --full run stays within minutes; every leg reports the steps it timed
 LEG_STEPS = {"many": (3, 1), "long": (1, 0), "spec64": (1, 0)}
 
 
@@ -81,8 +88,15 @@ def parse():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--instances", type=int, default=1 << 20, help="instances per GPU (SURVEY §8(d) cfg4: 2^20)")
-    ap.add_argument("--legs", default="reference,spec,conn,connu,many,long,spec64,ref2c,spec2c",
-                    help="comma list of reference (the headline value), spec (SURVEY §8 F3 coin rounds), conn "
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline leg, run the other legs (--legs, default: all of them), the C-oracle "
+                         "CPU baseline and report the recorded rate of the reference's Python path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline leg's last timed step computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--legs", default=None,
+                    help="the first leg is the headline; more than one leg needs --full (default: reference, with "
+                         "--full every leg).  Comma list of "
+                         "reference (the headline value), spec (SURVEY §8 F3 coin rounds), conn "
                          "(connection-identity peers, what the shipped reference runs: SURVEY §8 F1), connu (the same "
                          "under per-link uniform[1,2] delays), many (the reference protocol to round cap 8), long (the "
                          "reference protocol to SURVEY cfg4's round cap 64), spec64 (SPEC to round cap 64), ref2c / "
@@ -91,8 +105,8 @@ def parse():
                     help="shorthand for --legs <mode> (the headline leg is the first one run)")
     ap.add_argument("--round-cap", type=int, default=1, help="round cap of every leg but many")
     ap.add_argument("--many-cap", type=int, default=MANY_CAP, help="round cap of the many leg")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline sample budget (0: skip)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU baseline sample budget (0: skip)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                     help="collective backend for N > 1: nccl (= RCCL over xGMI, one GPU per rank); gloo "
                          "only rehearses the multi-rank flow with several ranks sharing one GPU")
@@ -100,7 +114,16 @@ def parse():
                     help="initialise the process group (and run the statistics all-reduce) even at world size 1, "
                          "e.g. one RCCL rank under torch.distributed.run --nproc-per-node 1")
     a = ap.parse_args()
-    a.legs = [a.mode] if a.mode else [x for x in a.legs.split(",") if x]
+    if a.mode:
+        a.legs = [a.mode]
+    elif a.legs is None:
+        a.legs = list(LEGS) if a.full else ["reference"]
+    else:
+        a.legs = [x for x in a.legs.split(",") if x]
+    if not a.legs or any(x not in LEGS for x in a.legs):
+        ap.error("--legs: a comma list of %s" % ", ".join(LEGS))
+    if len(a.legs) > 1 and not a.full:
+        ap.error("a plain run times the headline leg only: --legs with more than one leg needs --full")
     return a
 
 
@@ -205,8 +228,38 @@ def add_stats(a, b):
     return st, [x + y for x, y in zip(a[1], b[1])]
 
 
-def run_leg(args, mode, world, rank, local, dist, coll_dev):
-    """Time one leg (K steps after W warmups, barrier + sync on both sides, max over ranks)."""
+DUMP_BLOCKS, DUMP_BLOCK = 64, 256      # --dump-outputs sample of a large batch: 64 seeded blocks of 256 instances
+
+
+def sample_outputs(eng):
+    """What a caller of the timed path reads from the engine after a step, for --dump-outputs:
+      sample_ids  [S] float64          global ids of the sampled instances: every instance of the engine up to
+                                       16384, else DUMP_BLOCKS blocks of DUMP_BLOCK drawn with a fixed seed
+      instances   [S, 8] float64       Engine.instances_array() of the sample (brc_instance_result fields)
+      replicas    [S, n, 8] float32    Engine.replicas_array() of the sample (brc_replica_result fields, < 2^16)
+    run_leg() adds stats [15] (brc_stats fields in declaration order), round_hist [66] (Engine.round_histogram)
+    and decisions [6] (Engine.decisions(): honest replicas that first decided "-1", "0", "1", "3", undecided
+    ones, disagreeing instances), float64 totals of the whole batch over all ranks.  35 MB at the full batch;
+    every count is an integer below 2^53 (2^24 in replicas), so the float arrays are exact."""
+    import numpy as np
+    from numpy.lib import recfunctions as rfn
+    total, first = eng.instances, eng.cfg.instance_offset
+    if total <= DUMP_BLOCKS * DUMP_BLOCK:
+        blocks = [(0, total)]
+    else:
+        starts = np.random.RandomState(SEED).choice(total // DUMP_BLOCK, DUMP_BLOCKS, replace=False)
+        blocks = [(int(b) * DUMP_BLOCK, DUMP_BLOCK) for b in sorted(starts)]
+    ids = np.concatenate([np.arange(b, b + c, dtype=np.float64) for b, c in blocks]) + first
+    inst = np.concatenate([rfn.structured_to_unstructured(eng.instances_array(b, c), dtype=np.float64)
+                           for b, c in blocks])
+    repl = np.concatenate([rfn.structured_to_unstructured(eng.replicas_array(b, c), dtype=np.float32)
+                           for b, c in blocks])
+    return {"sample_ids": ids, "instances": inst, "replicas": repl}
+
+
+def run_leg(args, mode, world, rank, local, dist, coll_dev, head=False):
+    """Time one leg (K steps after W warmups, barrier + sync on both sides, max over ranks).  head: the
+    headline leg, which times exactly --steps steps and feeds --dump-outputs."""
     from byzantinerandomizedconsensus_amd import shard
     per = args.instances
     first, count = shard.shard_range(per * world, world, rank)     # global instance ids of this rank
@@ -236,7 +289,7 @@ def run_leg(args, mode, world, rank, local, dist, coll_dev):
     kern = set()
 
     steps, warmup = args.steps, args.warmup
-    if mode in LEG_STEPS:
+    if mode in LEG_STEPS and not head:
         steps, warmup = min(steps, LEG_STEPS[mode][0]), min(warmup, LEG_STEPS[mode][1])
     for _ in range(warmup):
         one_step()
@@ -248,6 +301,7 @@ def run_leg(args, mode, world, rank, local, dist, coll_dev):
     barrier()
     elapsed = time.perf_counter() - t0
     kernel_ms = sum(kms) / len(kms)          # all tiles of one step (= one launch per tile)
+    outputs = sample_outputs(eng) if head and args.dump_outputs and rank == 0 else None
     if len(tiles) == 1:
         acc = collect(eng)                   # the last timed step's results
     else:                                    # one more (untimed) pass reads every tile's results
@@ -259,6 +313,16 @@ def run_leg(args, mode, world, rank, local, dist, coll_dev):
     eng.close()
     kernel = kern.pop() if len(kern) == 1 else "mixed"
     st, hist = shard.reduce_stats(acc[0], dist, device=coll_dev, hist=acc[1])
+    if outputs is not None:
+        import numpy as np
+        from byzantinerandomizedconsensus_amd import _lib as L
+        outputs["stats"] = np.array([st[k] for k, _ in L.Stats._fields_], dtype=np.float64)
+        outputs["round_hist"] = np.array(hist, dtype=np.float64)
+        outputs["decisions"] = np.array([st["dec_" + k] for k in ("-1", "0", "1", "3", "undecided")] +
+                                        [st["disagreements"]], dtype=np.float64)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
     elapsed = shard.max_over_ranks(elapsed, dist, device=coll_dev)
     kernel_ms = shard.max_over_ranks(kernel_ms, dist, device=coll_dev)
     decided, arrivals, cell_steps = st["decided"], st["arrivals"], st["cell_steps"]
@@ -390,8 +454,9 @@ def main():
             tdist.init_process_group("gloo")
         dist = tdist
 
-    legs = {mode: run_leg(args, mode, world, rank, local, dist, coll_dev) for mode in args.legs}
     head_mode = args.legs[0]
+    legs = {mode: run_leg(args, mode, world, rank, local, dist, coll_dev, head=mode == head_mode)
+            for mode in args.legs}
     head = legs[head_mode]
     out = None
     if rank == 0:
@@ -400,8 +465,8 @@ def main():
             "value": head["value"],
             "unit": "instances/s",
             "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
+            "steps": head["steps"],
+            "warmup": head["warmup"],
             "ms_per_step": head["ms_per_step"],
             "higher_is_better": True,
             "scaling": "weak",
@@ -424,9 +489,9 @@ def main():
         for mode, leg in legs.items():
             if mode != head_mode:
                 out[mode + "_leg"] = leg
-    if rank == 0 and world == 1 and not args.no_cpu and args.cpu_seconds > 0:     # N = 1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and args.cpu_seconds > 0:     # N = 1 only
         out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, head_mode, head["round_cap"])
-    if rank == 0 and head_mode == "reference" and args.round_cap == 1:
+    if args.full and rank == 0 and head_mode == "reference" and args.round_cap == 1:
         # the reference's own Python path cannot travel to the GPU box: its rate on this workload was
         # measured in the build container (tools/ref_cpu_rate.py) and is reported beside, not as, the baseline
         try:

@@ -25,14 +25,17 @@ def test_two_class_legs_mirror_their_step_kernel_legs():
         assert bench.LEGS[b][5] == "life"
         assert "two-class" in bench.workload_name(b, 1, 1 << 20)
         assert "step kernel" in bench.workload_name(a, 1, 1 << 20)
-    # the headline is the first leg of the default run
+    # the headline is the first leg of the default --full run, and the only leg of a plain run
     old = sys.argv
     try:
-        sys.argv = ["bench.py"]
+        sys.argv = ["bench.py", "--full"]
         args = bench.parse()
+        sys.argv = ["bench.py"]
+        plain = bench.parse()
     finally:
         sys.argv = old
     assert args.legs[0] == "reference" and {"ref2c", "spec2c"} <= set(args.legs)
+    assert plain.legs == ["reference"] and not plain.full
 
 
 def test_configs_two_class_rows_mirror_their_step_rows():

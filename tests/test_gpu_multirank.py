@@ -55,7 +55,8 @@ def _legs(d):
 
 @pytest.mark.gpu
 def test_two_ranks_equal_one_rank_over_the_same_global_ids():
-    bench_args = ["--steps", "1", "--warmup", "0", "--no-cpu", "--legs", "reference,spec,many,long,spec64,ref2c,spec2c"]
+    bench_args = ["--full", "--steps", "1", "--warmup", "0", "--no-cpu",
+                  "--legs", "reference,spec,many,long,spec64,ref2c,spec2c"]
     multi = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node", str(WORLD),
                   "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py",
                   "--gpus", str(WORLD), "--backend", "gloo", "--instances", str(PER_RANK)] + bench_args, 300)
@@ -82,7 +83,7 @@ def test_rccl_rank_equals_plain_run():
     bound to the GPU (`device_id`): the statistics go through the device all-reduce of
     `shard.reduce_stats` / `max_over_ranks` -- the 8-GPU path's collective, run on the one leased
     GPU -- and must equal the plain single-process run over the same global ids."""
-    bench_args = ["--steps", "1", "--warmup", "0", "--no-cpu", "--legs", "reference,spec,many",
+    bench_args = ["--full", "--steps", "1", "--warmup", "0", "--no-cpu", "--legs", "reference,spec,many",
                   "--instances", str(PER_RANK * WORLD)]
     rccl = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node", "1",
                  "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py",

@@ -5,7 +5,7 @@
 # steps:
 #   tests[=<pytest -k expr>]     the -m gpu suite (or a -k subset)          -> tests.log
 #   smoke                         __graft_entry__.smoke()                    -> smoke.log
-#   bench[=<bench.py args>]       bench.py (default args)                    -> bench.json
+#   bench[=<bench.py args>]       bench.py (bench=--full: every leg)         -> bench.json
 #   configs[=<names>]             configs.py [--only names]                  -> configs.jsonl
 #   collect=<ptag>,<inst>,<leg>,<kernel>[,<passes>]   profiles/collect.sh    -> collect_<ptag>.log
 #   ab=<tags>,<rounds>[,<bench args>]                 tools/ab.sh            -> ab.log
