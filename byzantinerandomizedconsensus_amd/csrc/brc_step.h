@@ -1444,9 +1444,11 @@ void brc_step(const Params* __restrict__ pp) {
                         RS |= r2;
                     }
                 }
-                es[0] = ES & 1u; es[1] = ES >> 16;
-                rs[0] = RS & 1u; rs[1] = RS >> 16;
-                dl[0] = DL & 1u; dl[1] = DL >> 16;
+                // ES, RS, DL hold bits 0 and 16 only: the low half is key 0's flag (a 16-bit operand select,
+                // no AND per flag)
+                es[0] = ES & 0xFFFFu; es[1] = ES >> 16;
+                rs[0] = RS & 0xFFFFu; rs[1] = RS >> 16;
+                dl[0] = DL & 0xFFFFu; dl[1] = DL >> 16;
             } else if constexpr (BEB) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
@@ -1524,13 +1526,16 @@ void brc_step(const Params* __restrict__ pp) {
                 // new word for open cells; the others keep theirs.  A count reaches 64 only when every
                 // sender's message of that type has arrived, so none is compared again: the stored
                 // counts saturate at 63 without changing any later transition
-                const uint32_t sends = ((es[i] ? ts : tE[i]) << C32_OE_SH) | ((rs[i] ? ts : tR[i]) << C32_OR_SH);
+                eb[i] = __ballot(es[i] != 0); rb[i] = __ballot(rs[i] != 0); db[i] = __ballot(dl[i] != 0);
+                // the send steps select on the ballots themselves (a second compare per flag otherwise);
+                // BEB sends nothing here, and its constant-false flags fold only in the plain form
+                const bool se = BEB ? es[i] != 0 : lane_in(eb[i]), sr = BEB ? rs[i] != 0 : lane_in(rb[i]);
+                const uint32_t sends = ((se ? ts : tE[i]) << C32_OE_SH) | ((sr ? ts : tR[i]) << C32_OR_SH);
                 if constexpr (PK)
                     nw[i] = ((PL >> (16 * i)) & 0xFFFFu) | (((PR >> (16 * i)) & 0xFFFFu) << C32_RC_SH) | sends;
                 else
                     nw[i] = fl[i] | (min(ec[i], 63u) << C32_EC_SH) | (min(rc[i], 63u) << C32_RC_SH) | sends;
                 wr[i] = opn[i];
-                eb[i] = __ballot(es[i] != 0); rb[i] = __ballot(rs[i] != 0); db[i] = __ballot(dl[i] != 0);
             }
             st_bcast += popc(eb[0]) + popc(rb[0]) + popc(eb[1]) + popc(rb[1]);
             st_del += popc(db[0]) + popc(db[1]);
