@@ -468,6 +468,10 @@ int brc_create(const brc_config* cfg, void** out) {
                               // per-link form: its HBM delivery ring is [RW][NK] bits per instance
                               !(e->life_pl && c.key_window * c.variants > 32);
         bool big = e->compact && c.key_window * c.variants > 32;          // the lean kernels take <= 32
+        // connection peers at NPAD = 64 with 8,192 key slots (Q * NV = 128): the step kernel's LDS carve
+        // (186 KB) exceeds a workgroup's 160 KB, the lifetime kernel's (HBM slot metadata) does not
+        const bool conn_big = !e->wide && c.peer_mode == BRC_PEER_CONNECTION && e->lds_bytes > 160 * 1024;
+        if (conn_big && eligible) big = true;
         if (!big && e->compact && c.peer_mode == BRC_PEER_SENDER && hipSetDevice(c.device) == hipSuccess) {
             // the step kernel's whole per-instance state (cells, slot metadata / generations / destinations,
             // activity ring) against 90 % of the device's TOTAL memory: the choice depends on the
@@ -485,7 +489,8 @@ int brc_create(const brc_config* cfg, void** out) {
         e->step_ok = !big;
         if (big && !e->life_cfg) {
             g_create_err = c.key_window * c.variants > 32
-                ? "key windows above 32 at n in 33..64 with sender peers run on the key-lifetime kernel only "
+                ? "key windows above 32 at n in 33..64 with sender peers (128 with connection peers) run on the "
+                  "key-lifetime kernel only "
                   "(consensus, Philox / loaded proposals, delay_max <= 8, constant or slow-set delays, no event log)"
                 : "the step kernel's cells do not fit in free device memory and the key-lifetime kernel cannot run "
                   "this configuration";
@@ -601,7 +606,7 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
     const brc_config& c = e->cfg;
     if (!e->step_ok && count) {
         e->err = "this engine runs on the key-lifetime kernel only (its step-kernel state does not fit the device, "
-                 "or a key window above 32 at n in 33..64 with sender peers): no injections";
+                 "or a key window above 32 at n in 33..64 with sender peers, of 128 with connection peers): no injections";
         return BRC_E_UNSUPPORTED;
     }
     const uint64_t all = (c.n >= 64) ? ~0ull : ((1ull << c.n) - 1);
@@ -796,7 +801,8 @@ int brc_run(void* h, uint32_t max_steps, uint32_t* running_left) {
     const bool life = e->life_cfg && e->fresh && no_inj && max_steps == 0 && !e->values_wide;
     if (!life && !e->step_ok) {
         e->err = "this engine runs on the key-lifetime kernel only (its step-kernel state does not fit, or a key "
-                 "window above 32 at n in 33..64 with sender peers): a fresh run to completion, no injections, "
+                 "window above 32 at n in 33..64 with sender peers, of 128 with connection peers): a fresh run to "
+                 "completion, no injections, "
                  "max_steps = 0, value ids < 4 (brc_reset first)";
         return BRC_E_UNSUPPORTED;
     }

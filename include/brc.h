@@ -93,8 +93,9 @@ typedef struct {
     uint32_t key_window;      /* Q: live phase indices per origin (2, 4, 8; 16 .. 128 with n <= 64 and the
                                  reference / best-effort protocols, whose phase leakage keeps up to ~17
                                  phases of one origin in flight by round 8 and 127 by round 64 under
-                                 slow-set D = 8; above 32 at n in 33..64 with sender peers: the
-                                 key-lifetime kernel only) */
+                                 slow-set D = 8; above 32 at n in 33..64 with sender peers, and
+                                 Q * NV = 128 at n in 33..64 with connection peers: the key-lifetime
+                                 kernel only) */
     uint32_t variants;        /* NV: key variants per origin (1, 2 or 4; Q*NV <= 8, <= 128 where Q may be) */
     uint32_t proposals;       /* BRC_PROPOSALS_* (consensus) */
     uint32_t byz_pattern;     /* BRC_BYZ_* applied to every instance */
@@ -214,8 +215,10 @@ int brc_last_kernel_ms(void* engine, float* ms);
  * is faster there); a run it cannot take (injections, max_steps > 0) goes to the step kernel.  Sender
  * peers whose step-kernel state (cells, slot arrays, activity ring) would exceed 90 % of the device's
  * TOTAL memory -- a choice fixed by the configuration and device model, not by what else holds memory
- * -- or whose key window is above 32 are lifetime-kernel-only: brc_inject returns BRC_E_UNSUPPORTED
- * and so does a run with max_steps > 0.  Before the first brc_run, brc_last_kernel reports the kernel a fresh run to
+ * -- or whose key window is above 32 are lifetime-kernel-only, and so are connection peers at n in
+ * 33..64 with Q * NV = 128 (8,192 key slots: the step kernel's LDS carve exceeds a workgroup's 160 KB):
+ * brc_inject returns BRC_E_UNSUPPORTED and so does a run with max_steps > 0; where the lifetime kernel
+ * cannot take such a configuration (BRC_KERNEL=step, an event log, ...) brc_create returns BRC_E_INVALID.  Before the first brc_run, brc_last_kernel reports the kernel a fresh run to
  * completion would launch.  The environment variable
  * BRC_KERNEL (read by brc_create) = life uses it for every eligible engine, = step never.  Its
  * results equal the step kernel's; its instances end final, so a later injection that would

@@ -180,9 +180,11 @@ def test_cfg5_n256_full_size(model, dmax):
 
 @pytest.mark.parametrize("mode", ["reference", "spec"])
 def test_cfg4_bench_batch_2p20_sampled(mode):
-    """The bench's own batches (2^20 instances in one launch: the reference protocol, and SPEC with
-    Q = 8 on 4-byte cells): instances sampled across the whole id range equal the oracle run alone
-    on their global id."""
+    """The bench's batch sizes (2^20 instances in one launch: the reference protocol, and SPEC with
+    Q = 8) on the engine's default kernel for them, the key-lifetime kernel -- bench.py times its spec
+    leg on the step kernel, which tests/test_gpu_life_windows.py::test_spec_deep_coin_rounds_both_kernels
+    holds to the lifetime kernel and the oracle: instances sampled across the whole id range equal the
+    oracle run alone on their global id."""
     L = _L()
     N = 1 << 20
     spec = mode == "spec"
@@ -308,7 +310,9 @@ def test_cfg4_many_rounds_2p20_one_launch():
 
 @pytest.mark.parametrize("leg", ["long", "spec64"])
 def test_cfg4_round_cap_64_2p20_bench_legs(leg):
-    """bench.py's long and spec64 legs at their timed size: SURVEY cfg4's round cap 64 at the full 2^20
+    """The configurations of bench.py's long and spec64 legs at their timed size, on the engine's default
+    kernel (the key-lifetime kernel; bench.py times spec64 on the step kernel, whose SPEC path at depth
+    tests/test_gpu_life_windows.py::test_spec_deep_coin_rounds_both_kernels checks): SURVEY cfg4's round cap 64 at the full 2^20
     instances per GPU, one launch each.  long: the reference protocol (the re-proposal loop
     core/byzantinerandomizedconsensus.py:96-106; by round 64 ~7,600 keys of one instance are live at
     once, so the key-lifetime kernel with a key window of 128, its slot metadata in HBM).  spec64: the
