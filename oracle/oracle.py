@@ -152,5 +152,6 @@ def run(spec, light=False, kinds=("deliver", "decide", "send")):
         dec = [[t, nd, r, values[v]] for t, nd, r, v in dec]
     return {"status": STATUS.get(res.status), "t_stop": res.t_stop, "msgs_sent": res.msgs_sent,
             "arrivals": res.arrivals, "cell_steps": res.cell_steps,
+            "counts": {"deliver": res.n_deliver, "decide": res.n_decide, "send": res.n_send},
             "events": {"deliver": rows(bufs[0], res.n_deliver, 4, "deliver"), "decide": dec,
                        "send": rows(bufs[2], res.n_send, 5, "send")}}

@@ -106,6 +106,98 @@ def run_batch(specs, key_window=None, event_capacity=1 << 21, device=0):
     return out
 
 
+def _loaded_proposals(specs):
+    """[instance][replica] value ids of the specs' propose actions (all at step 0; replicas that
+    propose nothing -- the Byzantine ones -- get id 0, which no kernel reads)."""
+    import numpy as np
+    arr = np.zeros((len(specs), specs[0]["n"]), dtype=np.int8)
+    for i, sp in enumerate(specs):
+        for a in sp.get("actions", []):
+            if a["kind"] == "propose":
+                assert a["t"] == 0, "loaded proposals start at step 0"
+                arr[i, a["node"]] = a["value"]
+    return arr
+
+
+def open_batch(specs, event_capacity=0, proposals="inject", byz_pattern=False, key_window=None, device=0):
+    """The engine of one batch (specs share _cfg_key, consecutive g), inputs in place, not yet run.
+
+    proposals: "inject" (every action of the specs is injected, as run_batch does), or the batch path
+    bench.py times: "philox" (BRC_PROPOSALS_PHILOX: the specs' propose actions must be the Philox draws,
+    specs.cons_spec's default) or "loaded" (brc_load_proposals of the specs' propose values); neither
+    injects the propose actions.  byz_pattern: the specs' Byzantine actions are the engine's own
+    BRC_BYZ_EQUIVOCATE pattern (specs.equivocation_actions) and are not injected either.
+    At n in 33..64 the engine is created under BRC_KERNEL=step, so a run the key-lifetime kernel could
+    take stays on the step kernel."""
+    import os
+    sp0 = specs[0]
+    assert all(_cfg_key(sp) == _cfg_key(sp0) and sp["g"] == sp0["g"] + i for i, sp in enumerate(specs))
+    spec_mode = sp0["mode"] in ("spec", "spec_brb")
+    if spec_mode:
+        key_window = sp0["window"]
+    elif key_window is None:
+        key_window = sp0.get("key_window") or 8 // sp0.get("nv", 1)
+    protocol = {"spec": "consensus", "spec_brb": "brb", "beb": "brb", "beb_consensus": "consensus"}.get(
+        sp0["mode"], sp0["mode"])
+    mode = L.MODE_SPEC if spec_mode else (L.MODE_BEB if sp0["mode"].startswith("beb") else L.MODE_REFERENCE)
+    batch = proposals != "inject"
+    assert proposals in ("inject", "philox", "loaded") and (batch or not byz_pattern)
+    kw = dict(n=sp0["n"], f=sp0["f"], instances=len(specs), protocol=protocol, seed=sp0["seed"],
+              delay_model=sp0["delay_model"], delay_max=sp0["dmax"], delay_const=sp0.get("dconst", 1),
+              round_cap=sp0.get("round_cap", 0), step_cap=sp0.get("step_cap", 10000), key_window=key_window,
+              variants=sp0.get("nv", 1), byzantine=sp0.get("byzantine", ()), event_capacity=event_capacity,
+              instance_offset=sp0["g"], device=device, mode=mode,
+              peer_mode=L.PEER_CONNECTION if sp0.get("peer_mode") == "connection" else L.PEER_SENDER,
+              coin_seed=sp0.get("coin_seed", 0), general_keys=sp0.get("general_keys", False),
+              proposals={"inject": L.PROPOSALS_NONE, "philox": L.PROPOSALS_PHILOX, "loaded": L.PROPOSALS_LOADED}[proposals],
+              byz_pattern=L.BYZ_EQUIVOCATE if byz_pattern else L.BYZ_NONE)
+    force = 33 <= sp0["n"] <= 64
+    old = os.environ.get("BRC_KERNEL")
+    if force:
+        os.environ["BRC_KERNEL"] = "step"
+    try:
+        eng = Engine(**kw)
+    finally:
+        if force:
+            os.environ.pop("BRC_KERNEL", None)
+            if old is not None:
+                os.environ["BRC_KERNEL"] = old
+    try:
+        if proposals == "loaded":
+            eng.load_proposals(_loaded_proposals(specs))
+        inj = []
+        for i, sp in enumerate(specs):
+            skip = (("propose",) if batch else ()) + (("byz", "byz_key") if byz_pattern else ())
+            inj += _injections(dict(sp, actions=[a for a in sp.get("actions", []) if a["kind"] not in skip]), i)
+        eng.inject(inj)
+    except Exception:
+        eng.close()
+        raise
+    return eng
+
+
+def read_state(eng, specs):
+    """Every bulk output of a batch: instances_result(), replicas(), stats(), and under the consensus
+    protocol round_histogram(66) and decisions() (8 labels where the specs use VALUES8; None under BRB)."""
+    out = {"inst": eng.instances_result(), "reps": eng.replicas(), "stats": eng.stats(), "hist": None, "dec": None}
+    if eng.cfg.protocol == L.PROTO_CONSENSUS:
+        out["hist"] = eng.round_histogram(66)
+        values = specs[0].get("values") or ()
+        out["dec"] = eng.decisions(tuple(values)) if len(values) == 8 else eng.decisions()
+    return out
+
+
+def run_batch_noevents(specs, proposals="inject", byz_pattern=False, key_window=None, event_capacity=0, device=0):
+    """run_batch's sibling for the builds bench.py times: the batch runs with event_capacity = 0 (the
+    EV = false kernel instantiations; run_batch and everything on top of it launch the EV = true ones)
+    on the step kernel, and returns read_state().  event_capacity > 0 runs the same batch, same inputs,
+    on the EV = true twin."""
+    with open_batch(specs, event_capacity, proposals, byz_pattern, key_window, device) as eng:
+        eng.run()
+        assert eng.last_kernel() == "step", "the batch left the step kernel"
+        return read_state(eng, specs)
+
+
 def run_specs(specs, **kw):
     """Run any list of specs, batching compatible ones; results in input order."""
     groups = defaultdict(list)
