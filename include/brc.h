@@ -174,6 +174,8 @@ typedef struct {
 
 int brc_create(const brc_config* cfg, void** engine);
 int brc_load_proposals(void* engine, const int8_t* proposals /* [instances][n] value ids */);
+/* Per-instance Byzantine masks: replaces the mask of every instance (brc_config.byzantine_mask is not ORed
+ * in); bits at and above n are ignored; under BRC_BYZ_EQUIVOCATE the pattern is expanded again. */
 int brc_load_byzantine(void* engine, const uint64_t* byz_masks /* [instances][(n + 63) / 64] */);
 int brc_inject(void* engine, const brc_injection* list, size_t count);
 int brc_run(void* engine, uint32_t max_steps, uint32_t* running_left);

@@ -21,11 +21,12 @@ def sort_result(res):
     return out
 
 
-def _cfg_key(sp):
+def _cfg_key(sp, masks=True):
+    """masks = False: without the Byzantine list (batches whose masks are loaded per instance)."""
     return (sp["n"], sp["f"], sp["mode"], sp.get("nv", 1), sp["seed"], sp["delay_model"], sp["dmax"],
             sp.get("dconst", 1), sp.get("round_cap", 0), sp.get("step_cap", 10000),
-            tuple(sorted(sp.get("byzantine", []))), sp.get("window"), sp.get("coin_seed"), sp.get("peer_mode", "sender"),
-            sp.get("key_window"), sp.get("general_keys", False))
+            tuple(sorted(sp.get("byzantine", []))) if masks else None, sp.get("window"), sp.get("coin_seed"),
+            sp.get("peer_mode", "sender"), sp.get("key_window"), sp.get("general_keys", False))
 
 
 def _injections(sp, local):
@@ -90,6 +91,17 @@ def run_batch(specs, key_window=None, event_capacity=1 << 21, device=0):
         evs = eng.events()
     finally:
         eng.close()
+    per = instance_events(evs, specs)
+    out = []
+    for i, sp in enumerate(specs):
+        r = res[i]
+        out.append(sort_result({"status": r["status"], "t_stop": r["t_stop"], "msgs_sent": r["msgs_sent"],
+                                "arrivals": r["arrivals"], "events": per[i], "cell_steps": r["cell_steps"]}))
+    return out
+
+
+def instance_events(evs, specs):
+    """Engine.events() split per instance into the harness's deliver / decide / send lists (device order)."""
     per = [{"deliver": [], "decide": [], "send": []} for _ in specs]
     for (inst, t, kind, node, typ, a, b, _v) in evs:
         if kind == L.EV_DELIVER:
@@ -98,12 +110,28 @@ def run_batch(specs, key_window=None, event_capacity=1 << 21, device=0):
             per[inst]["decide"].append([t, node, a, specs[inst]["values"][b]])
         elif kind == L.EV_SEND:                # first broadcasts (copies: L.EV_COPY, wire export only)
             per[inst]["send"].append([t, node, typ, a, b])
-    out = []
+    return per
+
+
+def mask_words(specs, garbage=None):
+    """brc_load_byzantine's argument for the specs' own Byzantine lists: [instance][(n + 63) // 64] u64 words,
+    the caller's stride (the engine keeps NPAD / 64 words per instance).  garbage: a seed; every bit at or
+    above n is then drawn at random (the engine masks them off, brc_internal.h word_mask)."""
+    import random
+
+    import numpy as np
+    n = specs[0]["n"]
+    words = (n + 63) // 64
+    rng = random.Random(garbage)
+    arr = np.zeros((len(specs), words), dtype=np.uint64)
     for i, sp in enumerate(specs):
-        r = res[i]
-        out.append(sort_result({"status": r["status"], "t_stop": r["t_stop"], "msgs_sent": r["msgs_sent"],
-                                "arrivals": r["arrivals"], "events": per[i], "cell_steps": r["cell_steps"]}))
-    return out
+        m = sum(1 << b for b in sp.get("byzantine", []))
+        assert m < 1 << n
+        if garbage is not None:
+            m |= rng.getrandbits(64 * words - n) << n if 64 * words > n else 0
+        for w in range(words):
+            arr[i, w] = (m >> (64 * w)) & 0xFFFFFFFFFFFFFFFF
+    return arr
 
 
 def _loaded_proposals(specs):
@@ -119,7 +147,8 @@ def _loaded_proposals(specs):
     return arr
 
 
-def open_batch(specs, event_capacity=0, proposals="inject", byz_pattern=False, key_window=None, device=0):
+def open_batch(specs, event_capacity=0, proposals="inject", byz_pattern=False, key_window=None, device=0,
+               load_masks=False, cfg_byzantine=(), mask_garbage=None, kernel="step"):
     """The engine of one batch (specs share _cfg_key, consecutive g), inputs in place, not yet run.
 
     proposals: "inject" (every action of the specs is injected, as run_batch does), or the batch path
@@ -128,10 +157,16 @@ def open_batch(specs, event_capacity=0, proposals="inject", byz_pattern=False, k
     injects the propose actions.  byz_pattern: the specs' Byzantine actions are the engine's own
     BRC_BYZ_EQUIVOCATE pattern (specs.equivocation_actions) and are not injected either.
     At n in 33..64 the engine is created under BRC_KERNEL=step, so a run the key-lifetime kernel could
-    take stays on the step kernel."""
+    take stays on the step kernel; kernel = "life" creates it under BRC_KERNEL=life instead.
+    load_masks: the specs' Byzantine lists may differ.  The engine is created with cfg_byzantine as its
+    configuration mask and every spec's own list is loaded with brc_load_byzantine before anything else
+    (mask_words; mask_garbage sets the bits at and above n)."""
     import os
     sp0 = specs[0]
-    assert all(_cfg_key(sp) == _cfg_key(sp0) and sp["g"] == sp0["g"] + i for i, sp in enumerate(specs))
+    assert all(_cfg_key(sp, not load_masks) == _cfg_key(sp0, not load_masks) and sp["g"] == sp0["g"] + i
+               for i, sp in enumerate(specs))
+    assert load_masks or (not cfg_byzantine and mask_garbage is None)
+    assert kernel in ("step", "life")
     spec_mode = sp0["mode"] in ("spec", "spec_brb")
     if spec_mode:
         key_window = sp0["window"]
@@ -145,8 +180,8 @@ def open_batch(specs, event_capacity=0, proposals="inject", byz_pattern=False, k
     kw = dict(n=sp0["n"], f=sp0["f"], instances=len(specs), protocol=protocol, seed=sp0["seed"],
               delay_model=sp0["delay_model"], delay_max=sp0["dmax"], delay_const=sp0.get("dconst", 1),
               round_cap=sp0.get("round_cap", 0), step_cap=sp0.get("step_cap", 10000), key_window=key_window,
-              variants=sp0.get("nv", 1), byzantine=sp0.get("byzantine", ()), event_capacity=event_capacity,
-              instance_offset=sp0["g"], device=device, mode=mode,
+              variants=sp0.get("nv", 1), byzantine=cfg_byzantine if load_masks else sp0.get("byzantine", ()),
+              event_capacity=event_capacity, instance_offset=sp0["g"], device=device, mode=mode,
               peer_mode=L.PEER_CONNECTION if sp0.get("peer_mode") == "connection" else L.PEER_SENDER,
               coin_seed=sp0.get("coin_seed", 0), general_keys=sp0.get("general_keys", False),
               proposals={"inject": L.PROPOSALS_NONE, "philox": L.PROPOSALS_PHILOX, "loaded": L.PROPOSALS_LOADED}[proposals],
@@ -154,7 +189,7 @@ def open_batch(specs, event_capacity=0, proposals="inject", byz_pattern=False, k
     force = 33 <= sp0["n"] <= 64
     old = os.environ.get("BRC_KERNEL")
     if force:
-        os.environ["BRC_KERNEL"] = "step"
+        os.environ["BRC_KERNEL"] = kernel
     try:
         eng = Engine(**kw)
     finally:
@@ -163,6 +198,8 @@ def open_batch(specs, event_capacity=0, proposals="inject", byz_pattern=False, k
             if old is not None:
                 os.environ["BRC_KERNEL"] = old
     try:
+        if load_masks:
+            eng.load_byzantine(mask_words(specs, mask_garbage))
         if proposals == "loaded":
             eng.load_proposals(_loaded_proposals(specs))
         inj = []
@@ -187,15 +224,22 @@ def read_state(eng, specs):
     return out
 
 
-def run_batch_noevents(specs, proposals="inject", byz_pattern=False, key_window=None, event_capacity=0, device=0):
+def run_batch_noevents(specs, proposals="inject", byz_pattern=False, key_window=None, event_capacity=0, device=0,
+                       with_events=False, **masks):
     """run_batch's sibling for the builds bench.py times: the batch runs with event_capacity = 0 (the
     EV = false kernel instantiations; run_batch and everything on top of it launch the EV = true ones)
     on the step kernel, and returns read_state().  event_capacity > 0 runs the same batch, same inputs,
-    on the EV = true twin."""
-    with open_batch(specs, event_capacity, proposals, byz_pattern, key_window, device) as eng:
+    on the EV = true twin.  masks: open_batch's load_masks, cfg_byzantine, mask_garbage and kernel ("life":
+    the batch must run on the key-lifetime kernel).  with_events: (read_state(), the event log per instance,
+    every list sorted canonically)."""
+    kernel = masks.get("kernel", "step")
+    with open_batch(specs, event_capacity, proposals, byz_pattern, key_window, device, **masks) as eng:
         eng.run()
-        assert eng.last_kernel() == "step", "the batch left the step kernel"
-        return read_state(eng, specs)
+        assert eng.last_kernel() == kernel, "the batch left the %s kernel" % kernel
+        st = read_state(eng, specs)
+        if not with_events:
+            return st
+        return st, [sort_result({"events": ev})["events"] for ev in instance_events(eng.events(), specs)]
 
 
 def run_specs(specs, **kw):
