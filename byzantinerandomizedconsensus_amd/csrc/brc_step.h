@@ -1181,7 +1181,13 @@ void brc_step(const Params* __restrict__ pp) {
         if (inj_pos < inj_cnt) next = min(next, inj_at(inj_pos).t);
         if (next == 0xFFFFFFFFu) { if (running) status = BRC_QUIESCENT; break; }
         if (next > P.step_cap) { if (running) status = BRC_STEPCAP; break; }
+        // next == t: step t is entered again for actions injected with t == the item's step (brc.h brc_inject).
+        // Its ring row was cleared, so nothing marked there lands twice; what is derived from send times would
+        // land (and count) again -- the lean kernels' SEND arrivals (slot metadata) and the extra-SEND records'
+        // (xs_active): tsl, the step those two compare with, matches no link delay then
+        const bool reenter = next == t;
         t = LEAN ? uni32(next) : next;
+        const uint32_t tsl = reenter ? (t | 0x40000000u) : t;
         const uint32_t row = t & (RS - 1);
         if (LEAN && t - ep > C32_REBASE) rebase();
 
@@ -1206,7 +1212,7 @@ void brc_step(const Params* __restrict__ pp) {
             for (uint32_t w = 0; w < nkw; ++w) {
                 const uint64_t mE = uni64(s_act[(row * AT + 0) * nkw + w]), mR = uni64(s_act[(row * AT + 1) * nkw + w]);
                 const uint64_t m = s_meta[w * 64 + lane];
-                const uint32_t dt = t - m_tsend(m);                        // the delay of a SEND landing now
+                const uint32_t dt = tsl - m_tsend(m);                      // the delay of a SEND landing now
                 bool sl;
                 if constexpr (NLR != 0) {
                     // OV0 / OV1: the senders with a link of delay dly0 / dly1 to an honest receiver
@@ -1838,7 +1844,7 @@ void brc_step(const Params* __restrict__ pp) {
             // order), with the arrival count summed over its records; the key loop then skips it
             // (GEN16_XDONE, cleared after the loop).  No code of this is in the key loop's process().
             auto xs_active = [&](uint64_t w0) -> bool {
-                const uint32_t dt2 = t - ((uint32_t)(w0 >> 16) & 0xFFFFu);
+                const uint32_t dt2 = tsl - ((uint32_t)(w0 >> 16) & 0xFFFFu);
                 return dt2 - 1u < D && ((dset >> ((dt2 - 1u) & 31)) & 1u);
             };
             if (xs_n) {

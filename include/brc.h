@@ -116,6 +116,15 @@ typedef struct {
  * kernels (4-B cells, 2-bit ids). */
 enum { BRC_FLAG_GENERAL_KEYS = 1 };
 
+/* Injections may arrive between brc_run calls.  A record's time must not lie before the step its instance's wave
+ * item stands at (brc_instance_result.t_now once the engine has run): t < t_now is BRC_E_STATE.  t == t_now is
+ * accepted: the next brc_run enters step t again for the new actions only -- no message of that step arrives or
+ * is counted a second time -- and performs them after the actions step t has already seen.  An injection into a
+ * QUIESCENT instance re-opens it (RUNNING); DONE, STEPCAP, OVERFLOW and BADINJ instances refuse (BRC_E_STATE).
+ * A refused brc_inject call changes nothing, whatever valid records precede the refused one.
+ * Extra-SEND records (dst_mask below) leave their item's table when a later call adds one to the same item and
+ * the record's last possible arrival, its time + delay_max, lies before the item's step: only records in flight
+ * count against the 16. */
 typedef struct {
     uint32_t t;               /* action time: performed after step t, messages stamped t */
     uint16_t kind;            /* BRC_INJ_* */

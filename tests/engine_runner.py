@@ -242,6 +242,166 @@ def run_batch_noevents(specs, proposals="inject", byz_pattern=False, key_window=
         return st, [sort_result({"events": ev})["events"] for ev in instance_events(eng.events(), specs)]
 
 
+FINAL = ("done", "stepcap", "overflow", "bad_injection")      # the statuses brc_inject refuses
+
+
+def lookahead(k):
+    """Before every run(k) each instance has in the engine every action up to and including its k-th distinct
+    pending action time (the actions stamped 0 besides, before the first: that launch performs them without a step).  An item processes at most k steps per call and never steps past a record it holds, so
+    after the call it stands at or before that time: no item steps past an action still on the host."""
+    return dict(kind="lookahead", k=k)
+
+
+def at_now(marks):
+    """lookahead(1), except that every action of instance i stamped with a time in marks[i] stays on the host
+    until instances_result()[i]["t_now"] equals that time and is injected then, with t == t_now (what
+    network.Cluster.run does, in a batch).  The time must be a step at which that instance has arrivals:
+    run(1) then stops there."""
+    return dict(kind="at_now", k=1, marks=marks)
+
+
+def after_quiet(bounds, packed=False):
+    """bounds[i]: the first times of instance i's action groups 1, 2, ...  Group j + 1 is injected once the
+    instance is QUIESCENT after group j (which re-opens it).  packed = False: run() until nothing is running, and
+    every instance with a group left must then be QUIESCENT.  packed = True (several instances per wave item):
+    run(1) at a time, so that the group lands while the item still stands at the step the instance went quiet at,
+    and a sibling of the same item must be RUNNING at that moment."""
+    return dict(kind="after_quiet", bounds=bounds, packed=packed)
+
+
+def drive_interleaved(eng, specs, policy, skip=(), trace=None):
+    """Feed the specs' actions to an open, fresh engine in pieces (policy: lookahead, at_now, after_quiet) and run
+    it to the end.  Returns (read_state(), the event log per instance, sorted canonically; None without a log).
+    Each instance's expanded injections stay on the host in time order and go in in that order, so the records
+    of one instance reach the kernel in the order of a one-shot injection.  With an event log, events_since drains
+    it after every slice: the total never decreases and the pieces add up to the final events().
+    trace (a dict): slices, pieces, the (instance, t) of every at_now injection and every re-opening."""
+    from collections import Counter
+    trace = {} if trace is None else trace
+    trace.update(slices=0, pieces=0, at_now=[], reopened=[], unconsumed=0)
+    count = len(specs)
+    lists = [_injections(dict(sp, actions=[a for a in sp.get("actions", []) if a["kind"] not in skip]), i)
+             for i, sp in enumerate(specs)]
+    assert all(a["t"] <= b["t"] for v in lists for a, b in zip(v, v[1:]))
+    log = eng.cfg.event_capacity > 0
+    drained, totals = [], [0]
+    ipw = 1 if specs[0]["n"] > 32 else 64 // max(4, 1 << (specs[0]["n"] - 1).bit_length())
+
+    def inject(batch):
+        if batch:
+            eng.inject(batch)
+            trace["pieces"] += 1
+
+    def run(k):
+        left = eng.run(k)
+        trace["slices"] += 1
+        if log:
+            evs, total = eng.events_since(len(drained))
+            assert total >= totals[-1] and total == len(drained) + len(evs), (total, totals[-1], len(drained), len(evs))
+            totals.append(total)
+            drained.extend(evs)
+        return left, eng.instances_result()
+
+    bound = specs[0].get("step_cap", 10000) + 8
+    if policy["kind"] == "after_quiet":
+        bounds = {i: sorted(b) for i, b in policy["bounds"].items()}
+        group = lambda i, r: sum(r["t"] >= b for b in bounds.get(i, ()))   # noqa: E731
+        cur = [0] * count
+        inject([r for i, v in enumerate(lists) for r in v if group(i, r) == 0])
+        for _ in range(bound):
+            left, res = run(1 if policy["packed"] else 0)
+            piece = []
+            for i in range(count):
+                if cur[i] >= len(bounds.get(i, ())):
+                    continue
+                if res[i]["status"] != "quiescent":
+                    assert policy["packed"] and res[i]["status"] == "running", (i, res[i], "not quiescent at a group's end")
+                    continue
+                nxt = [r for r in lists[i] if group(i, r) == cur[i] + 1]
+                assert nxt and nxt[0]["t"] > res[i]["t_now"], (i, cur[i], res[i])
+                if policy["packed"]:
+                    sib = [j for j in range(i - i % ipw, min(i - i % ipw + ipw, count)) if j != i]
+                    assert any(res[j]["status"] == "running" for j in sib), (i, "no sibling of the item is running")
+                piece += nxt
+                cur[i] += 1
+                trace["reopened"].append((i, res[i]["t_now"]))
+            inject(piece)
+            if left == 0 and not piece:
+                break
+        assert all(cur[i] == len(bounds.get(i, ())) for i in range(count)), cur
+    else:
+        k = policy["k"]
+        marks = policy.get("marks", {})
+        held = [[r for r in v if r["t"] in marks.get(i, ())] for i, v in enumerate(lists)]
+        free = [[r for r in v if r["t"] not in marks.get(i, ())] for i, v in enumerate(lists)]
+        # a node's repeated SEND of a key it has SENT to everyone travels on no link under sender peers: brc_inject
+        # accepts and drops it, so the engine does not stop at its time -- it is fed, but is no pending time
+        allm = (1 << specs[0]["n"]) - 1
+        for v in free:
+            sent = set()
+            for r in v:
+                if r["kind"] == L.INJ_SEND:
+                    r["noop"] = specs[0].get("peer_mode") != "connection" and (r["node"], r["kp"], r["s"]) in sent
+                    if r["dst"] == allm:
+                        sent.add((r["node"], r["kp"], r["s"]))
+        pos = [0] * count
+        # the first launch performs the actions stamped 0 before it counts a step: they go in with the first piece
+        tnow, status, started = [0] * count, ["running"] * count, False
+        left = 1
+        for _ in range(bound):
+            piece = []
+            for i in range(count):
+                if status[i] in FINAL:
+                    # the one-shot run ignores a stopped instance's later records: the tables have none
+                    trace["unconsumed"] += len(free[i]) - pos[i] + len(held[i])
+                    pos[i], held[i] = len(free[i]), []
+                    continue
+                while started and pos[i] < len(free[i]) and free[i][pos[i]].get("noop") and free[i][pos[i]]["t"] <= tnow[i]:
+                    pos[i] += 1                       # the engine went past a dropped record's time: nothing to feed
+                times = sorted({r["t"] for r in free[i][pos[i]:] if (started or r["t"] > 0) and not r.get("noop")} |
+                               {r["t"] for r in free[i][:pos[i]] if r["t"] > tnow[i] and not r.get("noop")})
+                limit = times[k - 1] if len(times) >= k else float("inf")
+                while pos[i] < len(free[i]) and (free[i][pos[i]]["t"] <= limit or not started and free[i][pos[i]]["t"] == 0):
+                    assert free[i][pos[i]]["t"] > tnow[i] or not started, (i, tnow[i], free[i][pos[i]])
+                    piece.append(free[i][pos[i]])
+                    pos[i] += 1
+                assert not held[i] or held[i][0]["t"] >= tnow[i], (i, tnow[i], "stepped past a held action")
+                now = [r for r in held[i] if r["t"] == tnow[i]] if started else []
+                if now:
+                    piece += now
+                    held[i] = [r for r in held[i] if r["t"] != tnow[i]]
+                    trace["at_now"].append((i, tnow[i]))
+            inject(piece)
+            if left == 0 and not piece:
+                break
+            left, res = run(k)
+            tnow, status, started = [r["t_now"] for r in res], [r["status"] for r in res], True
+        assert all(pos[i] == len(free[i]) and not held[i] for i in range(count)), (pos, held)
+    assert eng.last_kernel() == "step", "the batch left the step kernel"
+    st = read_state(eng, specs)
+    if not log:
+        return st, None
+    final = eng.events()
+    assert Counter(drained) == Counter(final) and totals[-1] == len(final), (len(drained), len(final), totals[-1])
+    return st, [sort_result({"events": ev})["events"] for ev in instance_events(final, specs)]
+
+
+def _unfed(specs):
+    return [dict(sp, actions=[]) for sp in specs]
+
+
+def run_batch_interleaved(specs, policy, event_capacity=0, proposals="inject", key_window=None, device=0, trace=None,
+                          **masks):
+    """run_batch_noevents(..., with_events=True) with the batch's actions fed in pieces while the engine runs
+    (drive_interleaved; policy: lookahead(k), at_now(marks), after_quiet(bounds)).  The engine is opened as
+    open_batch opens it (same keywords, BRC_KERNEL=step at n in 33..64), with nothing injected."""
+    skip = ("propose",) if proposals != "inject" else ()
+    with open_batch(_unfed(specs), event_capacity, proposals, False, key_window, device, **masks) as eng:
+        if proposals == "loaded":
+            eng.load_proposals(_loaded_proposals(specs))
+        return drive_interleaved(eng, specs, policy, skip, trace)
+
+
 def run_specs(specs, **kw):
     """Run any list of specs, batching compatible ones; results in input order."""
     groups = defaultdict(list)
