@@ -186,8 +186,15 @@ struct Engine {
     // injected SENDs per key (instance << 32 | kp << 16 | s): how many, and each sender's destinations
     std::unordered_map<uint64_t, uint32_t> send_count;
     std::unordered_map<uint64_t, std::vector<std::pair<uint32_t, uint64_t>>> send_dst;
-    struct XRec { uint32_t k, t, seg; uint64_t smask, dst; };
-    std::unordered_map<uint64_t, std::vector<XRec>> xrec;   // item -> extra-SEND records (P.xsend)
+    // type: 0 = an extra SEND; BRC_ECHO / BRC_READY = a Byzantine replica's message to a subset of the peers
+    struct XRec { uint32_t k, t, seg, type; uint64_t smask, dst; };
+    std::unordered_map<uint64_t, std::vector<XRec>> xrec;   // item -> records in flight (P.xsend)
+    // injected ECHO / READY of Byzantine replicas on the non-lean narrow kernels with sender peers, per
+    // msg_key(instance, node, type, kp, s): the links used so far, and whether some of them went through a record
+    // (the sending lane's cell then keeps no send step, and a later broadcast becomes a record too)
+    std::unordered_map<uint64_t, uint64_t> msg_used;
+    std::unordered_map<uint64_t, bool> msg_rec;
+    std::vector<uint64_t> hbyz;                  // host copy of the per-instance Byzantine masks [instance][bw]
     // key-lifetime kernel (brc_life.h): eligible configuration, engine fresh since create / reset,
     // and whether the last run used it (its instances are then final: no re-opening injections)
     bool life_cfg = false, fresh = true, life_done = false, last_life = false;
@@ -220,6 +227,11 @@ static int pick_npad(uint32_t n) {
 static uint64_t word_mask(uint32_t n, uint32_t w) {
     const uint32_t lo = 64 * w;
     return n >= lo + 64 ? ~0ull : (n <= lo ? 0ull : ((1ull << (n - lo)) - 1));
+}
+
+// (instance, node, type, key) of an injected ECHO / READY at n <= 64: node < 64, kp < 256, s < 2^16
+static uint64_t msg_key(uint64_t instance, uint32_t node, uint32_t type, uint32_t kp, uint32_t s) {
+    return (instance << 32) | ((uint64_t)node << 26) | ((uint64_t)(type == BRC_READY) << 25) | ((uint64_t)kp << 16) | s;
 }
 
 static int pick_dm(uint32_t d) { return d <= 4 ? 4 : d <= 8 ? 8 : 16; }
@@ -555,6 +567,7 @@ int brc_create(const brc_config* cfg, void** out) {
             for (uint32_t w = 0; w < e->bw; ++w)
                 bm[i * e->bw + w] = (w == 0 ? c.byzantine_mask : c.byzantine_mask_hi[w - 1]) & word_mask(c.n, w);
         if (hipMemcpy(e->byz, bm.data(), bm.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return fail(BRC_E_HIP);
+        e->hbyz = bm;
     }
     if (clear_state(e, true) != BRC_OK) return fail(BRC_E_HIP);
     e->pending.assign(e->nitems, {});
@@ -594,6 +607,7 @@ int brc_load_byzantine(void* h, const uint64_t* masks) {
         for (uint32_t w = 0; w < words; ++w) bm[i * e->bw + w] = masks[i * words + w] & word_mask(e->cfg.n, w);
     HIPCHK(e, hipMemcpyAsync(e->byz, bm.data(), bm.size() * 8, hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->hbyz = bm;
     if (e->cfg.byz_pattern) { int rc = apply_pattern(e); if (rc) return rc; }
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return BRC_OK;
@@ -618,6 +632,10 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
     std::vector<uint64_t> staged_item;
     std::unordered_map<uint64_t, uint32_t> new_count;                                   // this batch's SENDs
     std::unordered_map<uint64_t, std::vector<std::pair<uint32_t, uint64_t>>> new_dst;
+    std::unordered_map<uint64_t, uint64_t> new_used;                                    // this batch's ECHO / READY links
+    std::unordered_map<uint64_t, bool> new_rec;
+    // restricted ECHO / READY: the non-lean narrow step kernels with sender peers (brc_step.h record pre-pass)
+    const bool msg_records = !e->wide && !e->compact && c.peer_mode == BRC_PEER_SENDER;
     for (size_t i = 0; i < count; ++i) {
         const brc_injection& x = list[i];
         if (x.instance >= c.instances || x.node >= c.n || x.t > c.step_cap) { e->err = "injection out of range"; return BRC_E_INVALID; }
@@ -648,7 +666,42 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
             r.slot = (uint16_t)(x.kp * c.key_window + (x.s % c.key_window));
             if (x.kind == BRC_INJ_MSG) {
                 if (x.type != BRC_ECHO && x.type != BRC_READY) { e->err = "MSG type must be ECHO or READY"; return BRC_E_INVALID; }
-                if (!full) { e->err = "ECHO/READY injections must address every peer"; return BRC_E_UNSUPPORTED; }
+                if (!full && !msg_records) {
+                    e->err = c.peer_mode == BRC_PEER_CONNECTION
+                        ? "an ECHO / READY to a subset of the peers: not with connection peers (every message is a new "
+                          "peer there; the record pre-pass counts senders)"
+                        : e->wide ? "an ECHO / READY to a subset of the peers: not on the wide kernels (n > 64), whose "
+                                    "receivers ballot over the senders' cells"
+                                  : "an ECHO / READY to a subset of the peers: not on the lean kernels (n in 33..64 with "
+                                    "sender peers; BRC_FLAG_GENERAL_KEYS runs the general form)";
+                    return BRC_E_UNSUPPORTED;
+                }
+                const bool byz = (e->hbyz[x.instance * e->bw + x.node / 64] >> (x.node % 64)) & 1ull;
+                if (!full && !byz) {
+                    e->err = "an ECHO / READY to a subset of the peers needs a Byzantine sender: an honest replica's own "
+                             "later broadcast would need per-link suppression the cells do not have";
+                    return BRC_E_UNSUPPORTED;
+                }
+                if (msg_records && byz) {
+                    // the links (node, type, key) used before, this batch included.  A message to a subset, and every
+                    // later one of a (node, type, key) that had one, goes over the remaining links as a record of the
+                    // item's table (possibly over none: it still is an action of its step); a broadcast to every peer
+                    // with no record before it keeps the cell path, which uses every link
+                    const uint64_t m64 = msg_key(x.instance, x.node, x.type, x.kp, x.s);
+                    uint64_t used = 0;
+                    bool rec = false;
+                    for (const auto* mp : {&e->msg_used, &new_used}) {
+                        auto it = mp->find(m64);
+                        if (it != mp->end()) used |= it->second;
+                    }
+                    for (const auto* mp : {&e->msg_rec, &new_rec}) rec = rec || mp->count(m64);
+                    if (!full || rec) {
+                        r.dst &= ~used;
+                        r.restricted = (uint8_t)(1u | ((used == 0 && r.dst != 0) ? 2u : 0u));   // bit 1: a SEND event
+                        new_rec[m64] = true;
+                    }
+                    new_used[m64] |= r.dst;
+                }
             } else if (x.kind == BRC_INJ_SEND) {
                 // a second SEND of a key (another origin or the same, one payload string SENT again):
                 // an extra-SEND record on the non-lean step kernels; the lean and wide kernels model
@@ -708,14 +761,17 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
         staged.push_back(r);
         staged_item.push_back(item);
     }
-    // extra-SEND records (r.type bit 1) into their items' tables: a record of the same key, step and
-    // destinations without this sender takes it, else a new one (records whose arrivals all lie in
+    // extra-SEND records (r.type bit 1) and restricted ECHO / READY records (r.restricted) into their items'
+    // tables: a record of the same key, step, type and destinations without this sender takes it, else a new one (records whose arrivals all lie in
     // steps already run leave the table when it is rewritten); all-or-nothing (a batch that
     // overflows a table changes nothing)
     std::unordered_map<uint64_t, std::vector<Engine::XRec>> xnew;
     for (size_t i = 0; i < staged.size(); ++i) {
         const InjDev& r = staged[i];
-        if (r.kind != BRC_INJ_SEND || !(r.type & 2)) continue;
+        const bool xsend = r.kind == BRC_INJ_SEND && (r.type & 2);
+        const bool xmsg = r.kind == BRC_INJ_MSG && r.restricted && r.dst != 0;   // no link left: no record
+        if (!xsend && !xmsg) continue;
+        const uint32_t rtype = xmsg ? r.type : 0u;
         const uint64_t item = staged_item[i];
         if (!xnew.count(item)) {
             // the table is rewritten: records whose arrivals all lie in steps already run are
@@ -729,16 +785,17 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
         auto& v = xnew[item];
         int slot = -1;
         for (size_t j = 0; j < v.size(); ++j) {
-            if (v[j].k == r.slot && v[j].t == r.t && v[j].seg == r.seg && v[j].dst == r.dst && !((v[j].smask >> r.node) & 1ull)) {
+            if (v[j].k == r.slot && v[j].t == r.t && v[j].seg == r.seg && v[j].type == rtype && v[j].dst == r.dst &&
+                !((v[j].smask >> r.node) & 1ull)) {
                 slot = (int)j;
                 break;
             }
         }
-        const Engine::XRec nr = {r.slot, r.t, r.seg, 1ull << r.node, r.dst};
+        const Engine::XRec nr = {r.slot, r.t, r.seg, rtype, 1ull << r.node, r.dst};
         if (slot >= 0) v[slot].smask |= 1ull << r.node;
         else if (v.size() < XSEND_MAX) v.push_back(nr);
         else {
-            e->err = "more than " + std::to_string(XSEND_MAX) + " extra-SEND records in flight in one item";
+            e->err = "more than " + std::to_string(XSEND_MAX) + " extra-SEND / restricted ECHO / READY records in flight in one item";
             return BRC_E_UNSUPPORTED;
         }
     }
@@ -750,7 +807,7 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
         xbuf.resize(o + 3 * XSEND_MAX + 1, 0);
         for (size_t j = 0; j < kv.second.size(); ++j) {
             const auto& q = kv.second[j];
-            xbuf[o + 3 * j] = (uint64_t)q.k | ((uint64_t)q.t << 16) | ((uint64_t)q.seg << 40);
+            xbuf[o + 3 * j] = (uint64_t)q.k | ((uint64_t)q.t << 16) | ((uint64_t)q.seg << 40) | ((uint64_t)q.type << XS_TYPE_SH);
             xbuf[o + 3 * j + 1] = q.smask;
             xbuf[o + 3 * j + 2] = q.dst;
         }
@@ -761,6 +818,8 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
     }
     for (size_t i = 0; i < staged.size(); ++i) e->pending[staged_item[i]].push_back(staged[i]);
     for (const auto& kv : new_count) e->send_count[kv.first] += kv.second;
+    for (const auto& kv : new_used) e->msg_used[kv.first] |= kv.second;
+    for (const auto& kv : new_rec) e->msg_rec[kv.first] = true;
     for (auto& kv : new_dst) {
         auto& v = e->send_dst[kv.first];
         v.insert(v.end(), kv.second.begin(), kv.second.end());
@@ -877,6 +936,8 @@ int brc_reset(void* h) {
     e->send_count.clear();
     e->send_dst.clear();
     e->xrec.clear();
+    e->msg_used.clear();
+    e->msg_rec.clear();
     if (e->pattern_active) {
         e->pattern_active = false;
         rc = apply_pattern(e);

@@ -83,7 +83,9 @@ struct InjDev {       // 48 B, per item CSR, sorted by t
     uint16_t slot, s;
     uint8_t kind, type, seg, node;
     int8_t value;
-    uint8_t restricted;   // SEND to a strict subset of the peers (set by the host for n > 64)
+    uint8_t restricted;   // SEND to a strict subset of the peers (set by the host for n > 64); MSG: bit 0 = an
+                          // ECHO / READY on the links node -> dst only (a record of the item's table lands it),
+                          // bit 1 = the first link (node, type, key) ever used: a SEND event (brc_step.h)
     uint8_t pad[2];
     uint64_t dst;         // destinations 0..63 (the narrow kernel reads the first 24 B only)
     uint64_t dst_hi[3];   // destinations 64..255 (wide kernel)
@@ -138,8 +140,12 @@ __host__ __device__ inline uint32_t delay_values(uint32_t model, uint32_t dmax) 
     return model == BRC_DELAY_CONST ? 1u : model == BRC_DELAY_SLOWSET ? (dmax > 1 ? 2u : 1u) : dmax;
 }
 
-// Extra-SEND records per item (a payload SENT by several origins; brc_step.h): live at once
+// Extra-SEND records per item (a payload SENT by several origins; brc_step.h): live at once.  The table is
+// shared with the restricted ECHO / READY records of Byzantine replicas (one bound for both kinds).
 constexpr uint32_t XSEND_MAX = 16;
+// a record's first word: key slot | step << 16 | instance segment << 40 | message type << XS_TYPE_SH
+// (0: an extra SEND; BRC_ECHO / BRC_READY: a restricted message)
+constexpr uint32_t XS_TYPE_SH = 48;
 
 // Consensus value ids (core/byzantinerandomizedconsensus.py:57-60 keys its tables by payload string;
 // id 0 is str(NONE) == "-1"): 2 bits (3 strings + "-1") on the lean, wide and key-lifetime kernels,

@@ -710,6 +710,9 @@ void brc_step(const Params* __restrict__ pp) {
     // written by brc_inject), xs_n in use (P.xsn).  Sender j of a record lands on receiver d at
     // t + delay(j -> d), as the key's own SEND; SENDs of one key at one step to one destination set
     // share a record.  (Sender peers: brc_inject has removed the links a sender used before.)
+    // The same table holds a Byzantine replica's ECHOs / READYs to a subset of the peers (sender peers): word 0
+    // carries the message type at XS_TYPE_SH (0: a SEND), the sender mask the one replica.  Its cell keeps no
+    // send step for them -- a ballot over send steps would land the message on every receiver.
     uint32_t xs_n = LEAN ? 0u : uni32(gp(P.xsn)[item]);
     auto xs_ld = [&](uint32_t i) -> uint64_t { return uni64(gp(P.xsend)[item * (uint64_t)(3 * XSEND_MAX) + i]); };
 
@@ -1099,6 +1102,33 @@ void brc_step(const Params* __restrict__ pp) {
                 }
             } else if (r.kind == BRC_INJ_MSG) {
                 if constexpr (!LEAN) {
+                  if (r.restricted) {
+                    // a Byzantine replica's ECHO / READY on the links r.node -> r.dst only (sender peers; brc_inject
+                    // has removed the links that (node, type, key) used before and put the record in the item's
+                    // table, whose pre-pass lands it): here its message count, its SEND event (bit 1: the first link
+                    // (node, type, key) ever used), ring marks at t + the delays to its honest destinations, the
+                    // key's t_quiet.  The sending lane's cell is not touched.
+                    uint32_t myset = 0;
+                    if (mine && honest && ((r.dst >> d) & 1ull)) {
+                        uint32_t j = 0;
+                        for (uint32_t ds = dset; ds; ds &= ds - 1, ++j)
+                            if ((Lmask(j) >> r.node) & 1) myset = 1u << (__ffs(ds) - 1);
+                    }
+                    const uint32_t os = wave_or(myset);
+                    if (mine && d == 0) {
+                        const uint32_t k = r.slot;
+                        const uint64_t m = s_meta[mbase + k];
+                        if (m_s1(m) != r.s + 1u) {
+                            badinj = true;                       // no such key (as for a MSG to every peer)
+                        } else {
+                            if (t + hibit(os) > m_tquiet(m)) s_meta[mbase + k] = m_with_tquiet(m, t + hibit(os));
+                            mark_lane(k, os, r.type);
+                            st_msgs += __popcll(r.dst & all64);
+                            if (r.restricted & 2u) log_ev(BRC_EV_SEND, r.node, r.type, (k >> qsh), r.s, m_value(m));
+                        }
+                    }
+                    if (mine) q_until = max(q_until, t + hibit(os));
+                  } else {
                     // a run of MSG records at this step (within the staged window): every lane applies
                     // its own records at once, so their cell loads overlap (cfg3's equivocation pattern
                     // is 80 such records per wave at step 1)
@@ -1106,7 +1136,7 @@ void brc_step(const Params* __restrict__ pp) {
                     uint32_t p1 = inj_pos;
                     while (p1 < inj_cnt && p1 - injc_base < INJ_CACHE) {
                         const InjDev q = inj_at(p1);
-                        if (q.t != t || q.kind != BRC_INJ_MSG) break;
+                        if (q.t != t || q.kind != BRC_INJ_MSG || q.restricted) break;
                         ++p1;
                     }
                     inj_pos = p1;
@@ -1139,6 +1169,7 @@ void brc_step(const Params* __restrict__ pp) {
                             }
                         }
                     }
+                  }
                 } else {
                     msg_marks(r, mine, (mine && d == r.node) ? msg_cell(r) : false);
                 }
@@ -1603,10 +1634,12 @@ void brc_step(const Params* __restrict__ pp) {
                 }
             }
         };
-        // xsa: this lane's extra-SEND arrivals of key k (the pre-pass below; 0 in the key loop)
+        // xsa / xea / xra: this lane's arrivals of key k from the item's records -- extra SENDs, restricted
+        // ECHOs, restricted READYs (the pre-pass below; the constant 0 in the key loop)
         // always inlined: an outlined call (the event-log instantiations' choice) keeps every variable it
         // captures by reference in scratch memory
-        auto process = [&](const uint32_t k, const uint64_t wd, const uint32_t xsa) __attribute__((always_inline)) {
+        auto process = [&](const uint32_t k, const uint64_t wd, const uint32_t xsa, const uint32_t xea,
+                           const uint32_t xra) __attribute__((always_inline)) {
             // both LDS reads issue before either is waited on (k == NK, the trash row: junk, unused)
             const uint64_t m_raw = s_meta[mbase + k];
             const uint32_t gw_raw = s_gen[mbase + k];
@@ -1654,6 +1687,9 @@ void brc_step(const Params* __restrict__ pp) {
                     }
                 });
             }
+            // a Byzantine replica's restricted ECHOs / READYs (records): new senders on their links, as the
+            // cell path's (brc_inject keeps a link from carrying one message twice)
+            if constexpr (!LEAN) { ea += xea; ra += xra; }
             // SEND from the key's origin: arrives at t_send + delay(origin -> d)
             bool s_arr = false;
             const uint32_t dt = t - m_tsend(m);
@@ -1839,10 +1875,11 @@ void brc_step(const Params* __restrict__ pp) {
                 });
             }
         } else {
-            // Extra-SEND pre-pass (records of keys SENT again, rare): a key with extra SEND arrivals
-            // now is processed here, whole (its SENDs ahead of its ECHO / READY, the canonical
-            // order), with the arrival count summed over its records; the key loop then skips it
-            // (GEN16_XDONE, cleared after the loop).  No code of this is in the key loop's process().
+            // Record pre-pass (keys SENT again, a Byzantine replica's ECHO / READY to a subset of the peers:
+            // rare): a key with record arrivals now is processed here, whole (its SENDs ahead of its ECHOs
+            // ahead of its READYs, the canonical order), with the arrival counts summed per message type
+            // over its records; the key loop then skips it (GEN16_XDONE, cleared after the loop).  No code
+            // of this is in the key loop's process().
             auto xs_active = [&](uint64_t w0) -> bool {
                 const uint32_t dt2 = tsl - ((uint32_t)(w0 >> 16) & 0xFFFFu);
                 return dt2 - 1u < D && ((dset >> ((dt2 - 1u) & 31)) & 1u);
@@ -1858,16 +1895,20 @@ void brc_step(const Params* __restrict__ pp) {
                         seen = seen || ((uint32_t)(v0 & 0xFFFFu) == k && xs_active(v0));
                     }
                     if (seen) continue;
-                    uint32_t xsa = 0;
+                    uint32_t xsa = 0, xea = 0, xra = 0;
                     for (uint32_t j = i; j < xs_n; ++j) {
                         const uint64_t v0 = xs_ld(3 * j);
                         if ((uint32_t)(v0 & 0xFFFFu) != k || !xs_active(v0)) continue;
                         const uint32_t dt2 = t - ((uint32_t)(v0 >> 16) & 0xFFFFu), b2 = 1u << (dt2 - 1u);
                         const uint64_t snd = xs_ld(3 * j + 1), dst2 = xs_ld(3 * j + 2);
                         const bool mine2 = hon_run && seg == (int)((v0 >> 40) & 0xFF) && ((dst2 >> d) & 1ull);
-                        xsa += mine2 ? popc((T)(Lmask(popc(dset & (b2 - 1u))) & (T)snd)) : 0u;
+                        const uint32_t c = mine2 ? popc((T)(Lmask(popc(dset & (b2 - 1u))) & (T)snd)) : 0u;
+                        const uint32_t ty = (uint32_t)(v0 >> XS_TYPE_SH) & 3u;     // wave-uniform
+                        if (ty == BRC_ECHO) xea += c;
+                        else if (ty == BRC_READY) xra += c;
+                        else xsa += c;
                     }
-                    process(k, mycells[(size_t)k * (CW * 64)], xsa);
+                    process(k, mycells[(size_t)k * (CW * 64)], xsa, xea, xra);
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                     if (d == 0) s_gen[mbase + k] |= GEN16_XDONE;
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -1882,7 +1923,7 @@ void brc_step(const Params* __restrict__ pp) {
                 fetch(p + CHUNK, wB, kB);
                 Unrolled<CHUNK>::run([&](auto ci) {
                     constexpr int c = decltype(ci)::value;
-                    process(kA[c], wA[c], 0u);                   // padding slots: the trash row
+                    process(kA[c], wA[c], 0u, 0u, 0u);           // padding slots: the trash row
                 });
                 Unrolled<CHUNK>::run([&](auto ci) {
                     constexpr int c = decltype(ci)::value;

@@ -117,9 +117,15 @@ class Codec:
         """Engine injections replaying captured wire messages [t, src, dst, envelope] (from
         Byzantine or external nodes): each key whose origin is one of the captured senders is
         declared once (keys of other origins belong to simulated honest nodes, which create
-        them), then its SENDs (with their destination masks) and its ECHO / READY broadcasts."""
+        them), then its SENDs and its ECHO / READY messages, each with its destination mask.
+
+        An ECHO / READY group that reached only a subset of the peers (a faulty replica talking to half
+        the committee) becomes a restricted ``INJ_MSG``.  ``brc_inject`` accepts it from a Byzantine
+        sender on the non-lean narrow step kernels with sender peers (n <= 32, or n in 33..64 with
+        ``general_keys``); connection peers, the lean kernels (n in 33..64 without the flag), the wide
+        kernels (n > 64) and lifetime-kernel-only engines refuse it with ``E_UNSUPPORTED``
+        (include/brc.h, "Restricted ECHO / READY")."""
         from . import _lib as L
-        allm = (1 << self.n) - 1
         groups, declared, out = {}, set(), []
         senders = {w[1] for w in wire}
         for t, src, dst, env in sorted(wire):
@@ -135,9 +141,6 @@ class Codec:
                 out.append(dict(t=t, kind=L.INJ_SEND, instance=instance, node=src, kp=kp, s=s, value=g["value"],
                                 dst=g["mask"]))
             else:
-                if g["mask"] != allm:
-                    raise ValueError("ECHO/READY to a subset of the peers is not modelled (core/brbroadcast.py "
-                                     "broadcasts them to every peer)")
                 out.append(dict(t=t, kind=L.INJ_MSG, type=typ, instance=instance, node=src, kp=kp, s=s,
-                                value=g["value"], dst=allm))
+                                value=g["value"], dst=g["mask"]))
         return out

@@ -122,9 +122,26 @@ enum { BRC_FLAG_GENERAL_KEYS = 1 };
  * is counted a second time -- and performs them after the actions step t has already seen.  An injection into a
  * QUIESCENT instance re-opens it (RUNNING); DONE, STEPCAP, OVERFLOW and BADINJ instances refuse (BRC_E_STATE).
  * A refused brc_inject call changes nothing, whatever valid records precede the refused one.
- * Extra-SEND records (dst_mask below) leave their item's table when a later call adds one to the same item and
- * the record's last possible arrival, its time + delay_max, lies before the item's step: only records in flight
- * count against the 16. */
+ * Extra-SEND and restricted ECHO / READY records (dst_mask below) leave their item's table when a later call adds
+ * one to the same item and the record's last possible arrival, its time + delay_max, lies before the item's step:
+ * only records in flight count against the 16.
+ *
+ * Restricted ECHO / READY: a BRC_INJ_MSG whose dst_mask is a proper subset of the n peers -- a faulty replica that
+ * ECHOes or READYs a payload to part of the committee and stays silent towards the rest.  One message travels on
+ * each link node -> d for d in dst_mask and arrives at t + delay(node, d); msgs_sent grows by the links used
+ * (Byzantine destinations included).  Sender peers carry one (node, type, key) once per link: links an earlier
+ * BRC_INJ_MSG of that (node, type, key) used are dropped from a later one (after a broadcast to every peer it
+ * carries nothing and changes no counter; a broadcast after a restricted one goes over the remaining links).  One
+ * BRC_EV_SEND event is logged, for the first link (node, type, key) ever uses, at that record's step.  The key must
+ * exist (BRC_BADINJ otherwise, as for a message to every peer).
+ *   Supported: the non-lean narrow step kernels with sender peers -- n <= 32, and n in 33..64 under
+ *   BRC_FLAG_GENERAL_KEYS -- in every mode (REFERENCE, SPEC, BEB; broadcast and consensus; with or without an
+ *   event log), from a node that is Byzantine in its instance (brc_config.byzantine_mask, or the mask
+ *   brc_load_byzantine loaded).
+ *   Documented rejections, each BRC_E_UNSUPPORTED with the kernel family named in brc_last_error: an honest
+ *   sender (its own later broadcast would need per-link suppression the cells do not have); connection peers;
+ *   the lean kernels (n in 33..64 with sender peers, no flag); the wide kernels (n > 64); engines that run on
+ *   the key-lifetime kernel only (they take no injection at all). */
 typedef struct {
     uint32_t t;               /* action time: performed after step t, messages stamped t */
     uint16_t kind;            /* BRC_INJ_* */
@@ -137,13 +154,16 @@ typedef struct {
                                  (n <= 32, or connection peers at n <= 64; not BRC_MODE_SPEC), 0..3 on
                                  the others (n in 33..64 with sender peers, n > 64, SPEC); larger:
                                  BRC_E_INVALID.  The same range holds for brc_load_proposals */
-    uint64_t dst_mask;        /* BRC_INJ_SEND destinations 0..63; BRC_INJ_MSG must address all
-                                 peers (a restricted ECHO / READY: BRC_E_UNSUPPORTED).  A second
+    uint64_t dst_mask;        /* BRC_INJ_SEND / BRC_INJ_MSG destinations 0..63.  A second
                                  SEND of a key (another node, or the same again: one payload string
                                  SENT twice, one key in the reference) is an extra SEND on the
-                                 narrow kernels that keep 3-bit value ids (up to 16 extra-SEND
-                                 records in flight per wave item; it must not precede the key's
-                                 first SEND); BRC_E_UNSUPPORTED on the others */
+                                 narrow kernels that keep 3-bit value ids (it must not precede the
+                                 key's first SEND); BRC_E_UNSUPPORTED on the others.  A BRC_INJ_MSG
+                                 to a proper subset of the peers (restricted ECHO / READY, below) is
+                                 a record of the same table.  The table holds up to 16 records
+                                 (extra SENDs and restricted ECHOs / READYs together) in flight per
+                                 wave item (64 / NPAD instances, NPAD = n rounded up to 4, 8, 16,
+                                 32, 64); one more: BRC_E_UNSUPPORTED, nothing changed */
     uint64_t dst_mask_hi[3];  /* destinations 64..255 (n > 64), as byzantine_mask_hi */
 } brc_injection;
 
