@@ -15,6 +15,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <map>
 #include <string>
 #include <vector>
 #include <unordered_map>
@@ -194,7 +195,14 @@ struct Engine {
     // (the sending lane's cell then keeps no send step, and a later broadcast becomes a record too)
     std::unordered_map<uint64_t, uint64_t> msg_used;
     std::unordered_map<uint64_t, bool> msg_rec;
-    std::vector<uint64_t> hbyz;                  // host copy of the per-instance Byzantine masks [instance][bw]
+    // the same on the wide kernels under BRC_FLAG_WIDE_RECORDS (brc_step_wide.h REC): one instance per item, one
+    // sender per record, destination and used-link sets of bw words (four kept)
+    bool wide_rec = false;
+    struct WRec { uint32_t k, t, type, node; uint64_t dst[4]; };
+    struct WUsed { uint64_t w[4] = {0, 0, 0, 0}; bool rec = false; };
+    std::unordered_map<uint64_t, std::vector<WRec>> wrec;   // instance -> records in flight (P.xsend)
+    std::map<std::pair<uint64_t, uint64_t>, WUsed> wmsg;    // (instance, wmsg_key) -> links used, had a record
+    std::vector<uint64_t> hbyz;                 // host copy of the per-instance Byzantine masks [instance][bw]
     // key-lifetime kernel (brc_life.h): eligible configuration, engine fresh since create / reset,
     // and whether the last run used it (its instances are then final: no re-opening injections)
     bool life_cfg = false, fresh = true, life_done = false, last_life = false;
@@ -234,10 +242,17 @@ static uint64_t msg_key(uint64_t instance, uint32_t node, uint32_t type, uint32_
     return (instance << 32) | ((uint64_t)node << 26) | ((uint64_t)(type == BRC_READY) << 25) | ((uint64_t)kp << 16) | s;
 }
 
+// (node, type, key) of an injected ECHO / READY at n > 64: node < 256, kp < 1024, s < 2^16
+static uint64_t wmsg_key(uint32_t node, uint32_t type, uint32_t kp, uint32_t s) {
+    return ((uint64_t)node << 40) | ((uint64_t)(type == BRC_READY) << 32) | ((uint64_t)kp << 16) | s;
+}
+
 static int pick_dm(uint32_t d) { return d <= 4 ? 4 : d <= 8 ? 8 : 16; }
 
-static int launch_step(int npad, int dm, bool events, int mode, bool wv4, uint32_t blocks, uint32_t lds, hipStream_t st,
-                       const Params* P) {
+static int launch_step(int npad, int dm, bool events, int mode, bool wv4, bool rec, uint32_t blocks, uint32_t lds,
+                       hipStream_t st, const Params* P) {
+    if (rec) return npad == 128 ? launch_step_128x(dm, events, mode, blocks, lds, st, P)
+                                : launch_step_256x(dm, events, mode, blocks, lds, st, P);
     switch (npad) {
     case 4: return launch_step_4(dm, events, mode, blocks, lds, st, P);
     case 8: return launch_step_8(dm, events, mode, blocks, lds, st, P);
@@ -316,7 +331,7 @@ static int clear_state(Engine* e, bool full) {
     HIPCHK(e, hipMemsetAsync(e->cons1, 0, (size_t)e->nitems * e->lpi * 8, e->stream));
     HIPCHK(e, hipMemsetAsync(e->hmask, 0, (size_t)e->nitems * e->cons_bytes, e->stream));
     HIPCHK(e, hipMemsetAsync(e->gcount, 0, 8 * 8, e->stream));
-    if (!e->compact && !e->wide) HIPCHK(e, hipMemsetAsync(e->xsn, 0, (size_t)e->nitems * 4, e->stream));
+    if ((!e->compact && !e->wide) || e->wide_rec) HIPCHK(e, hipMemsetAsync(e->xsn, 0, (size_t)e->nitems * 4, e->stream));
     if (e->event_count) HIPCHK(e, hipMemsetAsync(e->event_count, 0, 8, e->stream));
     return BRC_OK;
 }
@@ -412,13 +427,21 @@ int brc_create(const brc_config* cfg, void** out) {
         c.key_window * c.variants > ((c.mode != BRC_MODE_SPEC && c.n <= 64) ? 128u : 8u) ||
         c.f >= c.n || (c.byz_pattern == BRC_BYZ_EQUIVOCATE && c.variants < 2) ||
         (c.byz_pattern != BRC_BYZ_NONE && c.byz_pattern != BRC_BYZ_EQUIVOCATE) ||
-        c.proposals > BRC_PROPOSALS_LOADED || c.mode > BRC_MODE_BEB || (c.flags & ~(uint32_t)BRC_FLAG_GENERAL_KEYS) ||
+        c.proposals > BRC_PROPOSALS_LOADED || c.mode > BRC_MODE_BEB ||
+        (c.flags & ~(uint32_t)(BRC_FLAG_GENERAL_KEYS | BRC_FLAG_WIDE_RECORDS)) ||
         // the general form at NPAD = 64 with sender peers is the reference protocol's (KMODE_XREF)
         ((c.flags & BRC_FLAG_GENERAL_KEYS) && c.n > 32 && c.n <= 64 && c.peer_mode == BRC_PEER_SENDER &&
          c.mode != BRC_MODE_REFERENCE) ||
         (c.n > 64 && c.mode == BRC_MODE_SPEC && c.variants != 1))
     {
         g_create_err = "invalid configuration (see include/brc.h field ranges)";
+        return BRC_E_INVALID;
+    }
+    if ((c.flags & BRC_FLAG_WIDE_RECORDS) && (c.n <= 64 || c.peer_mode != BRC_PEER_SENDER)) {
+        g_create_err = c.n <= 64 ? "BRC_FLAG_WIDE_RECORDS is for the wide kernels (n > 64): the narrow kernels take restricted "
+                                   "ECHO / READY records without a flag (n <= 32, or BRC_FLAG_GENERAL_KEYS at n in 33..64)"
+                                 : "BRC_FLAG_WIDE_RECORDS needs sender peers: with connection peers every message is a new "
+                                   "peer, and the records count senders";
         return BRC_E_INVALID;
     }
     Engine* e = new Engine();
@@ -453,8 +476,10 @@ int brc_create(const brc_config* cfg, void** out) {
                                                 c.variants, e->rs, e->compact) * WPB;
     // wide kernel at 4 waves per SIMD (128 VGPRs): DM <= 8 without delay-code planes in registers (constant /
     // slow-set delays), sender peers, and LDS for four workgroups per CU
+    // BRC_FLAG_WIDE_RECORDS: the instantiations with the record path (3 waves per SIMD, or 2 at DM = 16, only)
+    e->wide_rec = e->wide && (c.flags & BRC_FLAG_WIDE_RECORDS);
     e->wide_wv4 = e->wide && e->dm <= 8 && !plane_model(c.delay_model) && c.peer_mode == BRC_PEER_SENDER &&
-                  e->lds_bytes <= 40u * 1024u;
+                  e->lds_bytes <= 40u * 1024u && !e->wide_rec;
     e->nval = value_ids(!e->compact && !e->wide);
     e->cons_bytes = cons_bytes_per_item(spec, e->wide, e->lpi, e->msize, c.key_window, c.variants, e->nval);
     // key-lifetime kernel (brc_life.h): NPAD = 64 consensus under a two-class delay model with D <= 8
@@ -540,8 +565,10 @@ int brc_create(const brc_config* cfg, void** out) {
         {(void**)&e->dring, (e->life_cfg && e->life_pl) ? (size_t)e->nitems * e->life_rw * e->nkw * 64 * 8 : 8},
         {(void**)&e->lmeta, (e->life_cfg && life_hbm_meta(c.key_window, e->life_pl)) ? (size_t)e->nitems * e->NK * 8 : 8},
         // extra-SEND records: the non-lean narrow kernels only (the lean and wide kernels refuse extra SENDs)
-        {(void**)&e->xsend, (e->compact || e->wide) ? 8 : (size_t)e->nitems * XSEND_MAX * 24},
-        {(void**)&e->xsn, (e->compact || e->wide) ? 8 : (size_t)e->nitems * 4},
+        // ... and the wide kernels' restricted ECHO / READY records, for engines created with BRC_FLAG_WIDE_RECORDS
+        {(void**)&e->xsend, e->wide_rec ? (size_t)e->nitems * XSEND_MAX * WREC_W * 8
+                                        : (e->compact || e->wide) ? 8 : (size_t)e->nitems * XSEND_MAX * 24},
+        {(void**)&e->xsn, (!e->wide_rec && (e->compact || e->wide)) ? 8 : (size_t)e->nitems * 4},
     };
     for (auto& a : allocs)
         if (hipMalloc(a.p, std::max<size_t>(a.bytes, 8)) != hipSuccess) {
@@ -636,6 +663,9 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
     std::unordered_map<uint64_t, bool> new_rec;
     // restricted ECHO / READY: the non-lean narrow step kernels with sender peers (brc_step.h record pre-pass)
     const bool msg_records = !e->wide && !e->compact && c.peer_mode == BRC_PEER_SENDER;
+    // ... and the wide kernels of an engine created with BRC_FLAG_WIDE_RECORDS (sender peers: brc_create)
+    std::map<std::pair<uint64_t, uint64_t>, Engine::WUsed> new_wmsg;
+    auto any4 = [](const uint64_t* w) { return (w[0] | w[1] | w[2] | w[3]) != 0; };
     for (size_t i = 0; i < count; ++i) {
         const brc_injection& x = list[i];
         if (x.instance >= c.instances || x.node >= c.n || x.t > c.step_cap) { e->err = "injection out of range"; return BRC_E_INVALID; }
@@ -666,7 +696,7 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
             r.slot = (uint16_t)(x.kp * c.key_window + (x.s % c.key_window));
             if (x.kind == BRC_INJ_MSG) {
                 if (x.type != BRC_ECHO && x.type != BRC_READY) { e->err = "MSG type must be ECHO or READY"; return BRC_E_INVALID; }
-                if (!full && !msg_records) {
+                if (!full && !msg_records && !e->wide_rec) {
                     e->err = c.peer_mode == BRC_PEER_CONNECTION
                         ? "an ECHO / READY to a subset of the peers: not with connection peers (every message is a new "
                           "peer there; the record pre-pass counts senders)"
@@ -701,6 +731,27 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
                         new_rec[m64] = true;
                     }
                     new_used[m64] |= r.dst;
+                }
+                if (e->wide_rec && byz) {
+                    // the same over bw destination words (the words past bw stay zero)
+                    const auto wk = std::make_pair((uint64_t)x.instance, wmsg_key(x.node, x.type, x.kp, x.s));
+                    Engine::WUsed u;
+                    for (const auto* mp : {&e->wmsg, &new_wmsg}) {
+                        auto it = mp->find(wk);
+                        if (it == mp->end()) continue;
+                        for (int w = 0; w < 4; ++w) u.w[w] |= it->second.w[w];
+                        u.rec = u.rec || it->second.rec;
+                    }
+                    uint64_t* dw[4] = {&r.dst, &r.dst_hi[0], &r.dst_hi[1], &r.dst_hi[2]};
+                    if (!full || u.rec) {
+                        const bool first = !any4(u.w);
+                        for (int w = 0; w < 4; ++w) *dw[w] &= ~u.w[w];
+                        const uint64_t left[4] = {*dw[0], *dw[1], *dw[2], *dw[3]};
+                        r.restricted = (uint8_t)(1u | ((first && any4(left)) ? 2u : 0u));   // bit 1: a SEND event
+                        u.rec = true;
+                    }
+                    for (int w = 0; w < 4; ++w) u.w[w] |= *dw[w];
+                    new_wmsg[wk] = u;
                 }
             } else if (x.kind == BRC_INJ_SEND) {
                 // a second SEND of a key (another origin or the same, one payload string SENT again):
@@ -766,7 +817,27 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
     // steps already run leave the table when it is rewritten); all-or-nothing (a batch that
     // overflows a table changes nothing)
     std::unordered_map<uint64_t, std::vector<Engine::XRec>> xnew;
-    for (size_t i = 0; i < staged.size(); ++i) {
+    std::unordered_map<uint64_t, std::vector<Engine::WRec>> wnew;   // the wide kernels' tables, by the same rules
+    for (size_t i = 0; e->wide_rec && i < staged.size(); ++i) {
+        const InjDev& r = staged[i];
+        const uint64_t dst[4] = {r.dst, r.dst_hi[0], r.dst_hi[1], r.dst_hi[2]};
+        if (r.kind != BRC_INJ_MSG || !r.restricted || !any4(dst)) continue;   // no link left: no record
+        const uint64_t item = staged_item[i];
+        if (!wnew.count(item)) {
+            std::vector<Engine::WRec> v0;
+            if (e->wrec.count(item))
+                for (const auto& q : e->wrec[item])
+                    if (!(its[item].initialized != 0 && q.t + c.delay_max < its[item].t)) v0.push_back(q);
+            wnew[item] = v0;
+        }
+        auto& v = wnew[item];
+        if (v.size() >= XSEND_MAX) {
+            e->err = "more than " + std::to_string(XSEND_MAX) + " restricted ECHO / READY records in flight in one instance";
+            return BRC_E_UNSUPPORTED;
+        }
+        v.push_back(Engine::WRec{r.slot, r.t, r.type, r.node, {dst[0], dst[1], dst[2], dst[3]}});
+    }
+    for (size_t i = 0; !e->wide_rec && i < staged.size(); ++i) {
         const InjDev& r = staged[i];
         const bool xsend = r.kind == BRC_INJ_SEND && (r.type & 2);
         const bool xmsg = r.kind == BRC_INJ_MSG && r.restricted && r.dst != 0;   // no link left: no record
@@ -816,7 +887,25 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
                                  e->stream));
         HIPCHK(e, hipMemcpyAsync(e->xsn + kv.first, &xbuf[o + 3 * XSEND_MAX], 4, hipMemcpyHostToDevice, e->stream));
     }
+    std::vector<uint64_t> wbuf;
+    wbuf.reserve(wnew.size() * (WREC_W * XSEND_MAX + 1));
+    for (auto& kv : wnew) {
+        e->wrec[kv.first] = kv.second;
+        const size_t o = wbuf.size();
+        wbuf.resize(o + WREC_W * XSEND_MAX + 1, 0);
+        for (size_t j = 0; j < kv.second.size(); ++j) {
+            const auto& q = kv.second[j];
+            wbuf[o + WREC_W * j] = (uint64_t)q.k | ((uint64_t)q.t << 16) | ((uint64_t)q.type << XS_TYPE_SH) |
+                                   ((uint64_t)q.node << WREC_NODE_SH);
+            for (int w = 0; w < 4; ++w) wbuf[o + WREC_W * j + 1 + w] = q.dst[w];
+        }
+        wbuf[o + WREC_W * XSEND_MAX] = kv.second.size();
+        HIPCHK(e, hipMemcpyAsync(e->xsend + kv.first * WREC_W * XSEND_MAX, &wbuf[o], WREC_W * XSEND_MAX * 8,
+                                 hipMemcpyHostToDevice, e->stream));
+        HIPCHK(e, hipMemcpyAsync(e->xsn + kv.first, &wbuf[o + WREC_W * XSEND_MAX], 4, hipMemcpyHostToDevice, e->stream));
+    }
     for (size_t i = 0; i < staged.size(); ++i) e->pending[staged_item[i]].push_back(staged[i]);
+    for (const auto& kv : new_wmsg) e->wmsg[kv.first] = kv.second;
     for (const auto& kv : new_count) e->send_count[kv.first] += kv.second;
     for (const auto& kv : new_used) e->msg_used[kv.first] |= kv.second;
     for (const auto& kv : new_rec) e->msg_rec[kv.first] = true;
@@ -909,8 +998,8 @@ int brc_run(void* h, uint32_t max_steps, uint32_t* running_left) {
         e->life_done = true;
     } else {
         rc = e->regmask ? launch_step_64r(e->dm, c.event_capacity != 0, kmode, blocks, e->lds_bytes, e->stream, e->dparams)
-                        : launch_step(e->npad, e->dm, c.event_capacity != 0, kmode, e->wide_wv4, blocks, e->lds_bytes,
-                                      e->stream, e->dparams);
+                        : launch_step(e->npad, e->dm, c.event_capacity != 0, kmode, e->wide_wv4, e->wide_rec, blocks,
+                                      e->lds_bytes, e->stream, e->dparams);
     }
     if (rc == BRC_E_INVALID) { e->err = "no kernel instantiation"; return rc; }
     if (rc) { e->err = std::string("step kernel launch: ") + hipGetErrorString(hipGetLastError()); return rc; }
@@ -938,6 +1027,8 @@ int brc_reset(void* h) {
     e->xrec.clear();
     e->msg_used.clear();
     e->msg_rec.clear();
+    e->wrec.clear();
+    e->wmsg.clear();
     if (e->pattern_active) {
         e->pattern_active = false;
         rc = apply_pattern(e);

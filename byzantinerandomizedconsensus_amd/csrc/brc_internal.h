@@ -129,7 +129,8 @@ struct Params {
     uint64_t* dring;              // per-link key-lifetime kernel: delivery bitmap ring [item][LIFE_RW or LIFE_RW16][nkw][64] (brc_life.h)
     uint32_t* lmeta;              // key-lifetime kernel, key windows >= 32: key-slot metadata + class delivery steps
                                   // [item][2][NK] u32 in HBM (brc_life.h)
-    uint64_t* xsend;              // non-lean step kernels: extra-SEND records [item][XSEND_MAX][3] (brc_step.h)
+    uint64_t* xsend;              // non-lean step kernels: extra-SEND records [item][XSEND_MAX][3] (brc_step.h);
+                                  // wide kernels with records: [instance][XSEND_MAX][WREC_W] (brc_step_wide.h)
     uint32_t* xsn;                // ... records in use per item
     unsigned long long* gcount;   // [0] cell_steps [1] arrivals [2] msgs [3] deliveries [4] lane loads [5] max s
                                   // [6] instances still running after the launch
@@ -146,6 +147,11 @@ constexpr uint32_t XSEND_MAX = 16;
 // a record's first word: key slot | step << 16 | instance segment << 40 | message type << XS_TYPE_SH
 // (0: an extra SEND; BRC_ECHO / BRC_READY: a restricted message)
 constexpr uint32_t XS_TYPE_SH = 48;
+// Wide kernels under BRC_FLAG_WIDE_RECORDS (brc_step_wide.h REC): the same table per instance holds restricted
+// ECHO / READY records only, WREC_W words each -- the first word as above with the one sender at WREC_NODE_SH (no
+// segment: one instance per workgroup), then the destination set's four words (words past NPAD / 64 are zero)
+constexpr uint32_t WREC_W = 5;
+constexpr uint32_t WREC_NODE_SH = 56;
 
 // Consensus value ids (core/byzantinerandomizedconsensus.py:57-60 keys its tables by payload string;
 // id 0 is str(NONE) == "-1"): 2 bits (3 strings + "-1") on the lean, wide and key-lifetime kernels,
@@ -280,5 +286,8 @@ int launch_step_64r(int dm, bool events, int mode, uint32_t blocks, uint32_t lds
 // wv4: the 4-waves-per-SIMD instantiation (wide_waves4: DM <= 8, no link-delay planes, sender peers)
 int launch_step_128(int dm, bool events, int mode, bool wv4, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
 int launch_step_256(int dm, bool events, int mode, bool wv4, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
+// ... with restricted ECHO / READY records (BRC_FLAG_WIDE_RECORDS; brc_kern_128x.hip / brc_kern_256x.hip)
+int launch_step_128x(int dm, bool events, int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
+int launch_step_256x(int dm, bool events, int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
 
 }  // namespace brc

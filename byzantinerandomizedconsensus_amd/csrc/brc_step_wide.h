@@ -61,7 +61,11 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t x) {
 // the instantiation for DM <= 8 under the constant / slow-set models (no delay-code planes in registers):
 // 128 VGPRs, and with the DM-sized ring and 2-word delivery bitmaps a cfg5 workgroup fits 40 KB of LDS, so
 // four workgroups share a CU (cfg5 const: 37.8 -> 31.9 ms, A/B round 5; uniform planes lose: 137.7 -> 139.8)
-template <int NPAD, int DM, bool EV, int MODE, int WV = 0>
+// REC (BRC_FLAG_WIDE_RECORDS): a Byzantine replica's ECHO / READY to a subset of the peers (include/brc.h,
+// "Restricted ECHO / READY").  Such a message has no cell representation -- the sender's cell holds one send step
+// for all its links -- so brc_inject keeps it as a record of the instance's table (P.xsend: WREC_W words each, P.xsn
+// in use) and each receiver lane adds its own hits to the ballot-derived counts.  false: none of this is compiled.
+template <int NPAD, int DM, bool EV, int MODE, int WV = 0, bool REC = false>
 __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ? BRC_WIDE_WAVES16 : BRC_WIDE_WAVES)) void brc_step_wide(const Params* __restrict__ pp) {
     const Params& P = *pp;
     constexpr bool SPEC = MODE == BRC_MODE_SPEC, BEB = MODE == BRC_MODE_BEB, CONN = MODE == KMODE_CONN;
@@ -133,6 +137,10 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
     if (d < 12) s_red[d] = 0;
     uint32_t any_rows = uni32(gp(P.actany)[inst]);
     uint32_t lane_rows = 0;
+    // REC: records in the instance's table (the host rewrites it between launches only) and where they start
+    uint32_t rec_n = 0;
+    if constexpr (REC) rec_n = min(uni32(gp(P.xsn)[inst]), XSEND_MAX);
+    const gptr_t<const uint64_t> recs = gp((const uint64_t*)P.xsend) + inst * (uint64_t)(WREC_W * XSEND_MAX);
 
     uint32_t status, t_stop, q_until;
     {
@@ -519,6 +527,35 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
                     }
                     q_until = max(q_until, t + hibit(os));
                 }
+            } else if (REC && r.kind == BRC_INJ_MSG && r.restricted) {
+                // a Byzantine replica's ECHO / READY on the links r.node -> dst only (brc_inject has removed the
+                // links (node, type, key) used before and put the record in the instance's table; process() lands
+                // it): here its message count, its SEND event (bit 1: the first link (node, type, key) ever used),
+                // ring marks at t + the delays to its honest destinations, the key's t_quiet.  The sender's cell is
+                // not touched.
+                const gptr_t<const uint64_t> rw = gp((const uint64_t*)(P.inj + inj_off + inj_pos - 1));
+                const uint64_t dw = rw[2 + wid];
+                uint32_t myset = 0;
+                if (mine && honest && ((dw >> lane) & 1ull)) myset = 1u << (link_delay(r.node) - 1);
+                const uint32_t os = block_or(myset);
+                if (mine) {
+                    const uint32_t k = r.slot;
+                    if (d == 0) {
+                        const uint64_t m = s_meta[k];
+                        if (m_s1(m) != r.s + 1u) {
+                            badinj = true;                       // no such key (as for a MSG to every peer)
+                        } else {
+                            if (t + hibit(os) > m_tquiet(m)) s_meta[k] = m_with_tquiet(m, t + hibit(os));
+                            mark_lane(k, os);
+                            uint32_t nd = 0;                     // links used, Byzantine destinations included
+#pragma unroll
+                            for (int w = 0; w < NW; ++w) nd += (uint32_t)__popcll(rw[2 + w]);
+                            st_msgs += nd;
+                            if (r.restricted & 2u) log_ev(BRC_EV_SEND, r.node, r.type, (k >> qsh), r.s, m_value(m));
+                        }
+                    }
+                    q_until = max(q_until, t + hibit(os));
+                }
             } else if (r.kind == BRC_INJ_MSG) {
                 const uint32_t k = r.slot;
                 bool sent = false;
@@ -600,8 +637,17 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
         if (inj_pos < inj_cnt) next = min(next, gp(P.inj)[inj_off + inj_pos].t);
         if (next == 0xFFFFFFFFu) { status = BRC_QUIESCENT; break; }
         if (next > P.step_cap) { status = BRC_STEPCAP; break; }
+        // REC: next == t is step t entered again for actions injected with t == the instance's step.  Its ring row was
+        // cleared, so no key is processed; the records compare with tsl, which matches no link delay then
+        const uint32_t tsl = (REC && next == t) ? (next | 0x40000000u) : next;
         t = next;
         const uint32_t row = t & (TS - 1);
+        // REC: the records (bit i = record i) whose messages can land now, sent 1 .. D steps ago; none with an empty table
+        uint32_t rec_act = 0;
+        if constexpr (REC) {
+            for (uint32_t i = 0; i < rec_n; ++i)
+                if (tsl - ((uint32_t)(uni64(recs[i * WREC_W]) >> 16) & 0xFFFFu) - 1u < D) rec_act |= 1u << i;
+        }
 
         // ================= BRB: this step's active key slots, as a key list in canonical (kp, s) order
         const uint32_t cells0 = st_cells;
@@ -814,6 +860,20 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
                     }
                 }
             }
+            if constexpr (REC) {
+                // restricted ECHO / READY records of this key: receiver d counts the ones whose destination set holds
+                // it and whose link delay node -> d has passed exactly now (lane-local: no exchange)
+                for (uint32_t ra_ = rec_act; ra_; ra_ &= ra_ - 1) {
+                    const gptr_t<const uint64_t> rp = recs + ((uint32_t)__ffs(ra_) - 1u) * WREC_W;
+                    const uint64_t w0 = uni64(rp[0]);
+                    if ((uint32_t)(w0 & 0xFFFFu) != k) continue;
+                    const uint64_t dw = rp[1 + wid];
+                    const bool hit = ((dw >> lane) & 1ull) &&
+                                     ((uint32_t)(w0 >> 16) & 0xFFFFu) + link_delay((uint32_t)(w0 >> WREC_NODE_SH) & 0xFFu) == tsl;
+                    if (((uint32_t)(w0 >> XS_TYPE_SH) & 3u) == BRC_ECHO) ea += hit ? 1u : 0u;
+                    else ra += hit ? 1u : 0u;
+                }
+            }
             BRC_WSTAMP(3);
             // SEND from the key's origin: arrives at t_send + delay(origin -> d)
             bool s_arr = false;
@@ -1022,9 +1082,9 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
     }
 }
 
-template <int NPAD, int DMX, bool EV, int MODE, int WV = 0>
+template <int NPAD, int DMX, bool EV, int MODE, int WV = 0, bool REC = false>
 int launch_wide_one(uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P) {
-    auto kern = brc_step_wide<NPAD, DMX, EV, MODE, WV>;
+    auto kern = brc_step_wide<NPAD, DMX, EV, MODE, WV, REC>;
     if (lds > 64 * 1024 &&
         hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return BRC_E_HIP;
@@ -1051,6 +1111,22 @@ int launch_step_wide(int dm, bool events, int mode, bool wv4, uint32_t blocks, u
         if (mode == BRC_MODE_BEB) return events ? launch_wide_one<NPAD, DMX, true, BRC_MODE_BEB>(blocks, lds, s, P) : launch_wide_one<NPAD, DMX, false, BRC_MODE_BEB>(blocks, lds, s, P); \
         if (mode == KMODE_CONN) return events ? launch_wide_one<NPAD, DMX, true, KMODE_CONN>(blocks, lds, s, P) : launch_wide_one<NPAD, DMX, false, KMODE_CONN>(blocks, lds, s, P); \
         return events ? launch_wide_one<NPAD, DMX, true, BRC_MODE_REFERENCE>(blocks, lds, s, P) : launch_wide_one<NPAD, DMX, false, BRC_MODE_REFERENCE>(blocks, lds, s, P); \
+    }
+    BRC_CASE(4) BRC_CASE(8) BRC_CASE(16)
+#undef BRC_CASE
+    return BRC_E_INVALID;
+}
+
+// the REC instantiations (BRC_FLAG_WIDE_RECORDS: sender peers, never WV = 4), in units of their own
+// (brc_kern_<NPAD>x.hip) so that the flagless units compile exactly what they did
+template <int NPAD>
+int launch_step_wide_rec(int dm, bool events, int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P) {
+#define BRC_CASE(DMX)                                                                                  \
+    if (dm == DMX) {                                                                                   \
+        if (mode == BRC_MODE_SPEC) return events ? launch_wide_one<NPAD, DMX, true, BRC_MODE_SPEC, 0, true>(blocks, lds, s, P) : launch_wide_one<NPAD, DMX, false, BRC_MODE_SPEC, 0, true>(blocks, lds, s, P); \
+        if (mode == BRC_MODE_BEB) return events ? launch_wide_one<NPAD, DMX, true, BRC_MODE_BEB, 0, true>(blocks, lds, s, P) : launch_wide_one<NPAD, DMX, false, BRC_MODE_BEB, 0, true>(blocks, lds, s, P); \
+        if (mode == BRC_MODE_REFERENCE) return events ? launch_wide_one<NPAD, DMX, true, BRC_MODE_REFERENCE, 0, true>(blocks, lds, s, P) : launch_wide_one<NPAD, DMX, false, BRC_MODE_REFERENCE, 0, true>(blocks, lds, s, P); \
+        return BRC_E_INVALID;                                                                          \
     }
     BRC_CASE(4) BRC_CASE(8) BRC_CASE(16)
 #undef BRC_CASE

@@ -122,9 +122,10 @@ class Codec:
         An ECHO / READY group that reached only a subset of the peers (a faulty replica talking to half
         the committee) becomes a restricted ``INJ_MSG``.  ``brc_inject`` accepts it from a Byzantine
         sender on the non-lean narrow step kernels with sender peers (n <= 32, or n in 33..64 with
-        ``general_keys``); connection peers, the lean kernels (n in 33..64 without the flag), the wide
-        kernels (n > 64) and lifetime-kernel-only engines refuse it with ``E_UNSUPPORTED``
-        (include/brc.h, "Restricted ECHO / READY")."""
+        ``general_keys``) and on the wide kernels (n > 64, destination masks of up to 256 bits) of an
+        engine created with ``wide_records``; connection peers, the lean kernels (n in 33..64 without
+        the flag), the wide kernels without theirs and lifetime-kernel-only engines refuse it with
+        ``E_UNSUPPORTED`` (include/brc.h, "Restricted ECHO / READY")."""
         from . import _lib as L
         groups, declared, out = {}, set(), []
         senders = {w[1] for w in wire}

@@ -108,6 +108,9 @@ def workloads(L):
         W["cfg5-" + name] = (6144, True, dict(base, n=256, f=85, seed=0x5EED0005, delay_model=model,
                                              delay_max=dmax, round_cap=1, key_window=8, mode=L.MODE_SPEC,
                                              coin_seed=COIN_SEED))
+        # the same with BRC_FLAG_WIDE_RECORDS and an empty record table: what opting in to restricted ECHO / READY
+        # records costs a run that injects none (no 4-waves-per-SIMD instantiation, one more word tested per step)
+        W["cfg5-" + name + "-rec"] = (6144, True, dict(W["cfg5-" + name][2], wide_records=True))
     return W
 
 

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define BRC_ABI_VERSION 7
+#define BRC_ABI_VERSION 8
 
 enum {
     BRC_OK = 0,
@@ -113,8 +113,13 @@ typedef struct {
  * ids (7 proposal strings besides "-1") and extra SENDs of one key (one payload SENT by several
  * origins, core/brbroadcast.py:74-79 keys by the payload string) -- what n <= 32 and connection peers
  * always have.  For the class API's single-instance clusters; the batched workloads keep the lean
- * kernels (4-B cells, 2-bit ids). */
-enum { BRC_FLAG_GENERAL_KEYS = 1 };
+ * kernels (4-B cells, 2-bit ids).
+ * BRC_FLAG_WIDE_RECORDS (v8): at n > 64 with sender peers (any mode, either protocol), run the wide kernel's
+ * instantiations that take restricted ECHO / READY records (below).  Opt-in: an engine without the flag launches
+ * the kernels it always did and refuses such records; with it the 4-waves-per-SIMD instantiations are not used and
+ * every step tests one more word, so a run without records is slightly slower.  With n <= 64 or
+ * connection peers brc_create fails with BRC_E_INVALID and a reason. */
+enum { BRC_FLAG_GENERAL_KEYS = 1, BRC_FLAG_WIDE_RECORDS = 2 };
 
 /* Injections may arrive between brc_run calls.  A record's time must not lie before the step its instance's wave
  * item stands at (brc_instance_result.t_now once the engine has run): t < t_now is BRC_E_STATE.  t == t_now is
@@ -135,13 +140,15 @@ enum { BRC_FLAG_GENERAL_KEYS = 1 };
  * BRC_EV_SEND event is logged, for the first link (node, type, key) ever uses, at that record's step.  The key must
  * exist (BRC_BADINJ otherwise, as for a message to every peer).
  *   Supported: the non-lean narrow step kernels with sender peers -- n <= 32, and n in 33..64 under
- *   BRC_FLAG_GENERAL_KEYS -- in every mode (REFERENCE, SPEC, BEB; broadcast and consensus; with or without an
+ *   BRC_FLAG_GENERAL_KEYS -- and the wide kernels (n > 64, sender peers) of an engine created with
+ *   BRC_FLAG_WIDE_RECORDS, in every mode (REFERENCE, SPEC, BEB; broadcast and consensus; with or without an
  *   event log), from a node that is Byzantine in its instance (brc_config.byzantine_mask, or the mask
- *   brc_load_byzantine loaded).
+ *   brc_load_byzantine loaded).  On the wide kernels one workgroup is one instance: up to 16 records in flight per
+ *   instance, over destination sets of up to 256 bits (dst_mask, dst_mask_hi).
  *   Documented rejections, each BRC_E_UNSUPPORTED with the kernel family named in brc_last_error: an honest
  *   sender (its own later broadcast would need per-link suppression the cells do not have); connection peers;
- *   the lean kernels (n in 33..64 with sender peers, no flag); the wide kernels (n > 64); engines that run on
- *   the key-lifetime kernel only (they take no injection at all). */
+ *   the lean kernels (n in 33..64 with sender peers, no flag); the wide kernels (n > 64) without
+ *   BRC_FLAG_WIDE_RECORDS; engines that run on the key-lifetime kernel only (they take no injection at all). */
 typedef struct {
     uint32_t t;               /* action time: performed after step t, messages stamped t */
     uint16_t kind;            /* BRC_INJ_* */
@@ -163,7 +170,8 @@ typedef struct {
                                  a record of the same table.  The table holds up to 16 records
                                  (extra SENDs and restricted ECHOs / READYs together) in flight per
                                  wave item (64 / NPAD instances, NPAD = n rounded up to 4, 8, 16,
-                                 32, 64); one more: BRC_E_UNSUPPORTED, nothing changed */
+                                 32, 64; n > 64 under BRC_FLAG_WIDE_RECORDS: per instance, restricted
+                                 ECHOs / READYs only); one more: BRC_E_UNSUPPORTED, nothing changed */
     uint64_t dst_mask_hi[3];  /* destinations 64..255 (n > 64), as byzantine_mask_hi */
 } brc_injection;
 
