@@ -181,9 +181,18 @@ struct Engine {
     Params hparams;
     std::vector<std::vector<InjDev>> pending;   // per item: uploaded-but-unconsumed + new
     bool inj_dirty = false, pattern_active = false;
-    // slot generation budget: reallocations of one key slot are bounded by max phase index / Q + 2
-    // per epoch (brc_reset to brc_reset); gen_base sums the epochs since the last full clear
+    // slot generation budget: the allocations of one key slot in an epoch (brc_reset to brc_reset) are bounded
+    // by gen_used() below; gen_base sums the epochs since the last full clear
     uint64_t gen_base = 0, gen_cur = 0;
+    // what bounds them (tagged kernels only; DESIGN.md section 3, "Key slots"), per epoch:
+    // gen_smax: the largest phase index a launch has reported; gen_extra: over the key slots, the most injected
+    // KEY / SEND records that can allocate one slot beyond one per key (under the consensus protocol every such
+    // record: the kernel may allocate the key itself); gen_passes: the most PROPOSE records of one replica (each
+    // starts its phase indices over), plus one when the engine proposes by itself
+    uint64_t gen_smax = 0, gen_extra = 0, gen_props = 0;
+    std::unordered_map<uint64_t, uint32_t> key_recs;    // instance << 32 | kp << 16 | s -> allocating records
+    std::unordered_map<uint64_t, uint32_t> slot_extra;  // instance << 32 | slot -> the slot's count for gen_extra
+    std::unordered_map<uint64_t, uint32_t> prop_recs;   // instance << 32 | node -> PROPOSE records
     // injected SENDs per key (instance << 32 | kp << 16 | s): how many, and each sender's destinations
     std::unordered_map<uint64_t, uint32_t> send_count;
     std::unordered_map<uint64_t, std::vector<std::pair<uint32_t, uint64_t>>> send_dst;
@@ -248,6 +257,18 @@ static uint64_t wmsg_key(uint32_t node, uint32_t type, uint32_t kp, uint32_t s) 
 }
 
 static int pick_dm(uint32_t d) { return d <= 4 ? 4 : d <= 8 ? 8 : 16; }
+
+// Slot generations (tagged kernels): how far this epoch can have advanced the tag of one key slot, plus one to
+// spare.  The kernels allocate a slot (gen + 1, brc_step.h) in send_key_now -- a replica's own key of phase index
+// s, once per s and pass, s rising within a pass (a PROPOSE starts the next pass) -- and in send_rec, for every
+// KEY record and every SEND record whose key is not declared-and-unsent.  With one record per key the records are
+// the keys of the slot, at most smax / Q + 1 of them; every further record is counted in gen_extra.
+static uint64_t gen_passes(const Engine* e) {
+    return std::max<uint64_t>(1, e->gen_props + (e->cfg.proposals != BRC_PROPOSALS_NONE ? 1u : 0u));
+}
+static uint64_t gen_used(const Engine* e) {
+    return gen_passes(e) * (e->gen_smax / e->cfg.key_window + 1) + e->gen_extra + 1;
+}
 
 static int launch_step(int npad, int dm, bool events, int mode, bool wv4, bool rec, uint32_t blocks, uint32_t lds,
                        hipStream_t st, const Params* P) {
@@ -905,6 +926,19 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
         HIPCHK(e, hipMemcpyAsync(e->xsn + kv.first, &wbuf[o + WREC_W * XSEND_MAX], 4, hipMemcpyHostToDevice, e->stream));
     }
     for (size_t i = 0; i < staged.size(); ++i) e->pending[staged_item[i]].push_back(staged[i]);
+    // the records that can allocate a key slot, for the generation budget (gen_used)
+    for (size_t i = 0; !(e->compact || e->wide) && i < staged.size(); ++i) {
+        const InjDev& r = staged[i];
+        const uint64_t in = staged_item[i] * e->ipw + r.seg;
+        if (r.kind == BRC_INJ_PROPOSE) {
+            e->gen_props = std::max<uint64_t>(e->gen_props, ++e->prop_recs[(in << 32) | r.node]);
+        } else if (r.kind == BRC_INJ_KEY || (r.kind == BRC_INJ_SEND && !(r.type & 2))) {
+            const uint32_t kp = r.slot / c.key_window;
+            const uint32_t nth = ++e->key_recs[(in << 32) | ((uint64_t)kp << 16) | r.s];
+            if (nth > 1 || c.protocol == BRC_PROTO_CONSENSUS)
+                e->gen_extra = std::max<uint64_t>(e->gen_extra, ++e->slot_extra[(in << 32) | r.slot]);
+        }
+    }
     for (const auto& kv : new_wmsg) e->wmsg[kv.first] = kv.second;
     for (const auto& kv : new_count) e->send_count[kv.first] += kv.second;
     for (const auto& kv : new_used) e->msg_used[kv.first] |= kv.second;
@@ -931,22 +965,34 @@ int brc_run(void* h, uint32_t max_steps, uint32_t* running_left) {
         e->err = "proposals not loaded";
         return BRC_E_STATE;
     }
-    // slot generations are 13-bit (wide kernel 11-bit) tags: past the budget a stale cell could
-    // read as current.  brc_reset clears fully once the budget is spent; a run that keeps stepping
-    // one simulation without resetting must stop here instead of risking the wrap.
-    // The lean (compact-cell) kernels, the wide kernel and the lifetime kernel keep no generation tags:
+    // slot generations are 13-bit tags: past the budget a stale cell could read as current.  brc_reset clears
+    // fully once gen_base + gen_cur reaches GEN_FULL_CLEAR, and so does the first run of an epoch whose staged
+    // records need it (nothing has run: every slot is free, only tags and stale cells are dropped), so gen_base
+    // stays below GEN_FULL_CLEAR and phase indices alone never get here (s_limit turns them into BRC_OVERFLOW).
+    // Injected records do: KEYs of one key allocate its slot once each, and nothing can clear an epoch under way.
+    // The lean (compact-cell) kernels, the wide kernels and the lifetime kernel keep no generation tags:
     // a slot's row is rewritten at allocation, so only the 14-bit phase-index snapshot bounds them.
     const uint64_t gen_hard = GEN_MASK - 2;
     const bool genfree = e->compact || e->wide;    // no cell generation tags (rows rewritten at allocation)
-    if (!genfree && e->gen_base + 2 >= gen_hard) {
-        e->err = "slot generation budget exhausted: call brc_reset";
-        return BRC_E_STATE;
-    }
-    int rc = upload_injections(e);
-    if (rc) return rc;
+    // (a fresh engine has consumed no record: the upload below leaves `pending` as it is, and an engine that is
+    // not fresh never takes the lifetime kernel)
     bool no_inj = true;
     for (const auto& v : e->pending) if (!v.empty()) { no_inj = false; break; }
     const bool life = e->life_cfg && e->fresh && no_inj && max_steps == 0 && !e->values_wide;
+    bool gen_clear = false;
+    if (!genfree && !life) {
+        gen_clear = e->fresh && e->gen_base > 0 && e->gen_base + gen_used(e) >= GEN_FULL_CLEAR;
+        if ((gen_clear ? 0 : e->gen_base) + gen_used(e) >= gen_hard) {
+            // gen_used counts a key's first record under BRB as its one allocation: on a fresh engine the 8188th KEY
+            // of one key (consensus protocol: the 8187th record of one slot) is the first to get here
+            e->err = "slot generation budget exhausted: call brc_reset (the records injected in this epoch can allocate "
+                     "one key slot more often than the " + std::to_string(gen_hard - 1 - (gen_clear ? 0 : e->gen_base)) +
+                     " generation tags left)";
+            return BRC_E_STATE;
+        }
+    }
+    int rc = upload_injections(e);
+    if (rc) return rc;
     if (!life && !e->step_ok) {
         e->err = "this engine runs on the key-lifetime kernel only (its step-kernel state does not fit, or a key "
                  "window above 32 at n in 33..64 with sender peers, of 128 with connection peers): a fresh run to "
@@ -957,6 +1003,12 @@ int brc_run(void* h, uint32_t max_steps, uint32_t* running_left) {
     if (!life) {
         rc = ensure_cells(e);
         if (rc) return rc;
+    }
+    if (gen_clear) {
+        rc = fill_cells(e);
+        if (rc) return rc;
+        HIPCHK(e, hipMemsetAsync(e->mgen, 0, (size_t)c.instances * e->NK * 4, e->stream));
+        e->gen_base = 0;
     }
     Params P;
     memset(&P, 0, sizeof(P));
@@ -974,9 +1026,14 @@ int brc_run(void* h, uint32_t max_steps, uint32_t* running_left) {
     P.nL = delay_values(c.delay_model, c.delay_max);
     P.event_cap = c.event_capacity;
     P.mode = c.mode; P.coin_seed = c.coin_seed;
-    // a slot allocated for phase index s has been reallocated at most gen_base + s/Q + 1 times
+    // a slot allocated for phase index s has been reallocated at most gen_base + passes * (s / Q + 1) + gen_extra
+    // times (gen_used; the budget check above keeps the difference positive)
     // (and phase indices stay below 2^14 - 1: the narrow kernel's consensus snapshot keeps s + 1 in 14 bits)
-    P.s_limit = genfree ? 0x3FFEu : (uint32_t)std::min<uint64_t>(0x3FFEull, (gen_hard - 1 - e->gen_base) * c.key_window);
+    // (the lifetime kernel reads no s_limit; elsewhere the budget check above keeps the difference positive)
+    const uint64_t gen_spent = e->gen_base + e->gen_extra;
+    P.s_limit = (genfree || life || gen_spent + 1 >= gen_hard)
+                    ? 0x3FFEu
+                    : (uint32_t)std::min<uint64_t>(0x3FFEull, (gen_hard - 1 - gen_spent) / gen_passes(e) * c.key_window);
     P.cells = e->cells; P.meta = e->meta; P.mgen = e->mgen; P.kdst = e->kdst;
     P.act = e->act; P.actany = e->actany; P.items = e->items;
     P.inst = e->inst; P.istats = e->istats; P.cons0 = e->cons0; P.cons1 = e->cons1; P.hmask = e->hmask;
@@ -1008,7 +1065,10 @@ int brc_run(void* h, uint32_t max_steps, uint32_t* running_left) {
     HIPCHK(e, hipEventElapsedTime(&e->last_ms, e->ev0, e->ev1));
     unsigned long long gc[8];
     HIPCHK(e, hipMemcpy(gc, e->gcount, sizeof(gc), hipMemcpyDeviceToHost));
-    if (!genfree) e->gen_cur = std::max<uint64_t>(e->gen_cur, gc[5] / c.key_window + 2);   // gc[5]: max phase index
+    if (!genfree && !life) {
+        e->gen_smax = std::max<uint64_t>(e->gen_smax, gc[5]);   // gc[5]: max phase index
+        e->gen_cur = std::max<uint64_t>(e->gen_cur, gen_used(e));
+    }
     if (running_left) *running_left = (uint32_t)gc[6];   // counted by the step kernel
     return BRC_OK;
 }
@@ -1027,6 +1087,10 @@ int brc_reset(void* h) {
     e->xrec.clear();
     e->msg_used.clear();
     e->msg_rec.clear();
+    e->gen_smax = e->gen_extra = e->gen_props = 0;
+    e->key_recs.clear();
+    e->slot_extra.clear();
+    e->prop_recs.clear();
     e->wrec.clear();
     e->wmsg.clear();
     if (e->pattern_active) {

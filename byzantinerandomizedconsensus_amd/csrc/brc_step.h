@@ -544,8 +544,10 @@ void brc_step(const Params* __restrict__ pp) {
         } else if (P.delay_model == BRC_DELAY_SLOWSET) {
             const uint32_t off = slow_offset(P.seed, g, n);
             const bool me_slow = ((uint32_t)d + n - off) % n < P.f;
-            // the slow set of this lane's instance: its segment's lanes with me_slow
-            const T slowm = (T)(__ballot(me_slow) >> segbase);
+            // the slow set of this lane's instance: its segment's lanes with me_slow.  NPAD = 4: T has 8 bits, and
+            // bits 4 .. 7 of the shifted ballot are the NEXT instance's slow lanes -- senders this one does not have
+            T slowm = (T)(__ballot(me_slow) >> segbase);
+            if constexpr (NPAD < 8 * sizeof(T)) slowm &= allm;
 #pragma unroll
             for (int i = 0; i < DM; ++i) {
                 if ((uint32_t)i + 1 == D) L[i] |= me_slow ? allm : slowm;

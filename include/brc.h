@@ -216,6 +216,18 @@ int brc_load_proposals(void* engine, const int8_t* proposals /* [instances][n] v
 int brc_load_byzantine(void* engine, const uint64_t* byz_masks /* [instances][(n + 63) / 64] */);
 int brc_inject(void* engine, const brc_injection* list, size_t count);
 int brc_run(void* engine, uint32_t max_steps, uint32_t* running_left);
+/* Back to step 0 with no injections, for the same global instances (brc_reset_at: for others).  Nothing bounds
+ * the number of resets, nor the KEY / SEND records injected over them: on the kernels whose cells carry a slot
+ * generation tag (n <= 32, connection peers, BRC_FLAG_GENERAL_KEYS) the engine counts the allocations every epoch
+ * can have made of one key slot and clears its cells fully, by itself, before a tag could come round.  Two things
+ * remain within ONE epoch (reset to reset), where nothing can be cleared:
+ *  - phase indices at or above s_limit = min(0x3FFE, (8188 - generations booked since the last full clear - extra
+ *    records of the epoch) / passes * key_window) stop their instance with BRC_OVERFLOW (passes: PROPOSE records
+ *    of one replica; below 6000 generations booked no full clear has happened yet, so s_limit can be as low as
+ *    about 2188 * key_window);
+ *  - brc_run is BRC_E_STATE ("slot generation budget exhausted") when the injected records of the epoch could
+ *    advance one slot's tag past the generations left: on a fresh engine 8188 KEY records of one key (8187
+ *    records of one slot under the consensus protocol), fewer after earlier epochs; brc_reset recovers. */
 int brc_reset(void* engine);
 int brc_read_instances(void* engine, uint64_t first, uint64_t count, brc_instance_result* out);
 int brc_read_replicas(void* engine, uint64_t first, uint64_t count, brc_replica_result* out /* [count][n] */);
