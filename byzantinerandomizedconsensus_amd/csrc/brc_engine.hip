@@ -494,7 +494,8 @@ int brc_create(const brc_config* cfg, void** out) {
     e->lds_bytes = e->wide ? lds_bytes_wide(e->npad, e->NK, e->nkw, xw,
                                             spec, c.key_window, e->rs)
                            : lds_bytes_per_wave(e->npad, e->NK, e->nkw, e->regmask ? 0u : nL, spec, c.key_window,
-                                                c.variants, e->rs, e->compact) * WPB;
+                                                c.variants, e->rs, e->compact,
+                                                typed_list(e->compact, c.event_capacity != 0, (int)c.mode)) * WPB;
     // wide kernel at 4 waves per SIMD (128 VGPRs): DM <= 8 without delay-code planes in registers (constant /
     // slow-set delays), sender peers, and LDS for four workgroups per CU
     // BRC_FLAG_WIDE_RECORDS: the instantiations with the record path (3 waves per SIMD, or 2 at DM = 16, only)

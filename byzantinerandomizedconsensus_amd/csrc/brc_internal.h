@@ -74,6 +74,19 @@ constexpr int CHUNK = BRC_CHUNK;            // narrow kernel: key slots whose ce
 #endif
 constexpr int LCHUNK = BRC_LCHUNK;          // ... on the lean kernels (4 or 8; A/B round 4: 8 is 0.9 % faster)
 constexpr int KPAD = CHUNK > LCHUNK ? CHUNK : LCHUNK;   // key-list padding entries: 2 KPAD
+#ifndef BRC_TYPED
+#define BRC_TYPED 1          // lean kernels without an event log (not BEB): the step's key list sorted by the message
+#endif                       // types landing on a key, one straight-line pair body per class (0: one mixed list)
+#ifndef BRC_TYPED_ER
+#define BRC_TYPED_ER 1       // ... with a class of its own for keys receiving ECHO and READY in one step (0: general body)
+#endif
+// the kernels with the type-sorted list (brc_step.h TYPED); mode: a BRC_MODE_* / KMODE_* value of a lean kernel
+__host__ __device__ constexpr bool typed_list(bool lean, bool events, int mode) {
+    return BRC_TYPED && lean && !events && mode != BRC_MODE_BEB;
+}
+// ... their key-list entries beyond NK + 2 KPAD: each of the list's segments (brc_step.h TCLS <= 5 classes) is padded
+// to a whole chunk, fewer than KPAD entries each
+constexpr uint32_t KL_TYPED_PAD = 5 * (KPAD - 1) + 1;
 #ifndef BRC_KL32_SPEC
 #define BRC_KL32_SPEC 0     // lean SPEC with u32 key-list entries too (1 KB more LDS per wave at Q = 8)
 #endif
@@ -194,13 +207,15 @@ constexpr uint32_t INJ_CACHE = 16;
 // u32 entries on the lean REFERENCE / BEB kernels; BRC_PSEG: one list per instance on the others) |
 // injc[INJ_CACHE][3] u64 (not on the lean kernels)
 __host__ __device__ inline uint32_t lds_bytes_per_wave(int npad, uint32_t NK, uint32_t nkw, uint32_t nL, bool spec,
-                                                       uint32_t Q, uint32_t nv, uint32_t rs, bool lean) {
+                                                       uint32_t Q, uint32_t nv, uint32_t rs, bool lean, bool typed) {
     const uint32_t ipw = 64 / (uint32_t)npad;
     const uint32_t msize = npad <= 8 ? 1 : (uint32_t)npad / 8;
     const uint32_t h_words = cons_words(spec, msize, Q, nv, value_ids(!lean));
     const uint32_t l_words = (nL * 64 * msize + 7) / 8;
     // (lean REFERENCE / BEB kernels: u32 entries, brc_step.h KL_*)
-    const uint32_t klist_u16 = (NK + 2 * KPAD) * ((lean && (!spec || BRC_KL32_SPEC)) ? 2u : lean ? 1u : act_types(false, ipw));
+    // (typed: + KL_TYPED_PAD entries, the chunk padding of the type-sorted list's segments, typed_list())
+    const uint32_t klist_u16 = (NK + 2 * KPAD + (typed ? KL_TYPED_PAD : 0u)) *
+                               ((lean && (!spec || BRC_KL32_SPEC)) ? 2u : lean ? 1u : act_types(false, ipw));
     const uint32_t gen_words = lean ? 0u : (ipw * NK + 3) / 4;   // lean kernels keep no slot generations
     const uint32_t dbits_words = (lean && spec) ? 0u : 64 * nkw;   // lean SPEC keeps them in HBM
     const uint32_t injc_words = lean ? 0u : 3 * INJ_CACHE;

@@ -368,6 +368,11 @@ __device__ __forceinline__ Ring16 ring_put(Ring16 r, uint32_t tl, uint32_t t, ui
 #ifndef BRC_PK
 #define BRC_PK 1             // lean kernels: a key pair's cell updates in the two 16-bit halves of a register
 #endif
+// key-list classes (BRC_TYPED, brc_internal.h): the general body (any other combination, restricted SENDs), then one
+// segment per type combination -- ECHO, READY, SEND and (BRC_TYPED_ER) ECHO + READY; tcls_tb = the class's TB_* bits
+// as a compile-time constant (-1: read from the entry)
+constexpr int TCLS = BRC_TYPED_ER ? 5 : 4;
+constexpr int tcls_tb(int c) { return c == 1 ? 2 : c == 2 ? 4 : c == 3 ? 1 : c == 4 ? 6 : -1; }
 
 // Two u16 lanes per register (v_pk_*_u16): the lean kernels update the cells of a key PAIR with one
 // instruction per operation.  Every operand stays below 2^15 (set sizes <= 127, thresholds <= 65),
@@ -393,10 +398,12 @@ __device__ __forceinline__ uint32_t pk2(uint32_t x) { return x | (x << 16); }   
 // metadata read once per chunk, exec-masked cell stores and (NLR = 2) link-delay masks held in
 // registers -- the headline configuration has exactly two link delays.
 #ifdef BRC_STAMPS
-#define BRC_NSTAMPS 12
+#define BRC_NSTAMPS 24
 // dev-only: [0..7] section timers (s_memtime ticks): step head + key list, key loop, consensus
 // words, actions, stop checks, consensus snapshot, consensus row clears, key-loop tail (ring rows);
-// [8..11] lean key-steps: processed, without arrivals, reaching only delivered cells, fully updated
+// [8..11] lean key-steps: processed, without arrivals, reaching only delivered cells, fully updated;
+// [12..19] lean key-list entries by type bits (TB_*) 0..7; [20] pairs of two keys with different type bits,
+// [21] pairs whose second key is padding
 __device__ unsigned long long brc_stamps[BRC_NSTAMPS];
 #endif
 template <int NPAD, int MODE> constexpr bool lean_kernel() { return NPAD == 64 && MODE != KMODE_CONN && MODE != KMODE_XREF; }
@@ -419,6 +426,7 @@ void brc_step(const Params* __restrict__ pp) {
     const Params& P = *pp;
     constexpr bool SPEC = MODE == BRC_MODE_SPEC, BEB = MODE == BRC_MODE_BEB, CONN = MODE == KMODE_CONN;
     constexpr bool LEAN = lean_kernel<NPAD, MODE>();
+    constexpr bool TYPED = typed_list(LEAN, EV, MODE);   // type-sorted key list, one pair body per class
     static_assert(NLR == 0 || (LEAN && NLR == 2), "register delay masks: lean kernels, two delays");
     constexpr uint32_t CW = CONN ? 5 : 1;        // u64 words per cell (CONN: + ECHO and READY send rings)
     using T = typename MaskOf<NPAD>::type;
@@ -448,7 +456,7 @@ void brc_step(const Params* __restrict__ pp) {
     const uint32_t h_words = cons_words(SPEC, (uint32_t)sizeof(T), Q, NV, NVAL);
     const bool seen_on = NV > 1;                 // SPEC: host sets needed only with key variants
     const uint32_t l_words = (nL * 64 * (uint32_t)sizeof(T) + 7) / 8;
-    uint64_t* s_meta = smem + (size_t)wid * (lds_bytes_per_wave(NPAD, NK, nkw, nL, SPEC, Q, NV, RS, LEAN) / 8);
+    uint64_t* s_meta = smem + (size_t)wid * (lds_bytes_per_wave(NPAD, NK, nkw, nL, SPEC, Q, NV, RS, LEAN, TYPED) / 8);
     uint64_t* s_act = s_meta + IPW * NK;
     // this step's deliveries, per lane: LDS, or (DBG: lean SPEC, whose LDS limits residency) one
     // HBM row per wave written once per key word from a register (dacc) -- no LDS at all
@@ -1193,13 +1201,15 @@ void brc_step(const Params* __restrict__ pp) {
 
 #ifdef BRC_STAMPS
     uint64_t stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t kcount[4] = {0, 0, 0, 0};
+    uint32_t kcount[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t stamp_prev = __builtin_amdgcn_s_memtime();
 #define BRC_STAMP(i) do { const uint64_t _n = __builtin_amdgcn_s_memtime(); stamp_acc[i] += _n - stamp_prev; stamp_prev = _n; } while (0)
 #define BRC_KCOUNT(i) (++kcount[i])
+#define BRC_KCOUNT_N(i, n) (kcount[i] += (n))
 #else
 #define BRC_STAMP(i) do {} while (0)
 #define BRC_KCOUNT(i) do {} while (0)
+#define BRC_KCOUNT_N(i, n) do {} while (0)
 #endif
     for (uint32_t it = 0; it < P.max_steps; ++it) {
         const bool running0 = status == BRC_RUNNING;
@@ -1233,16 +1243,27 @@ void brc_step(const Params* __restrict__ pp) {
         uint64_t dacc = 0;
         uint32_t dcur = NOKEY, dwm = 0;
         auto flush_dacc = [&](uint32_t wk, uint64_t v) {
-            if constexpr (DBG) gdbits[wk * 64] = v;
-            else s_dbits[wk * 64 + lane] = v;
+            // TYPED: the list is one ascending pass per class, so a key word can come up once per class: a word
+            // already written this step (dwm) gains the new deliveries, any other word is overwritten as before
+            if (TYPED && ((dwm >> wk) & 1u)) {
+                if constexpr (DBG) gdbits[wk * 64] = gdbits[wk * 64] | v;
+                else s_dbits[wk * 64 + lane] |= v;
+            } else {
+                if constexpr (DBG) gdbits[wk * 64] = v;
+                else s_dbits[wk * 64 + lane] = v;
+            }
             dwm |= 1u << wk;
         };
         uint32_t nkeys = 0, nks = 0;                // PSEG: nks = this instance's list length
+        // TYPED: class c's segment is list entries [sbase[c], sbase[c + 1]), its first scnt[c] real, the rest
+        // padding up to a whole chunk; nkeys = sbase[TCLS], the padded length
+        uint32_t sbase[TCLS + 1], scnt[TCLS];
         if constexpr (LEAN) {
             // typed marks: ECHO / READY rows; SEND arrivals from the slot's metadata -- the SEND of slot
             // k lands now at some receiver iff t - t_send is a delay of its sender's outset (reading the
             // next key word ahead measured no gain: A/B round 4)
-            for (uint32_t w = 0; w < nkw; ++w) {
+            // this lane's slot of key word w: its type bits (0: not listed) and its list entry
+            auto slot_entry = [&](const uint32_t w, uint32_t& ent, bool& restr) -> uint32_t {
                 const uint64_t mE = uni64(s_act[(row * AT + 0) * nkw + w]), mR = uni64(s_act[(row * AT + 1) * nkw + w]);
                 const uint64_t m = s_meta[w * 64 + lane];
                 const uint32_t dt = tsl - m_tsend(m);                      // the delay of a SEND landing now
@@ -1257,19 +1278,83 @@ void brc_step(const Params* __restrict__ pp) {
                     sl = m_s1(m) != 0 && dt1 < 32u && ((os >> (dt1 & 31u)) & 1u);
                 }
                 const uint32_t tb = (sl ? TB_S : 0u) | ((uint32_t)(mE >> lane) & 1u) * TB_E | ((uint32_t)(mR >> lane) & 1u) * TB_R;
+                restr = (m & M_RESTRICTED) != 0;
+                if constexpr (KL32) {
+                    const uint32_t sx = (tb & TB_S) ? (((m_sender(m) & 63u) << KL_SND_SH) | (((dt - 1u) & 15u) << KL_DT_SH) |
+                                                       (restr ? KL_RESTR : 0u)) : 0u;
+                    ent = (w * 64 + lane) | (tb << TB_SH) | sx;
+                } else {
+                    ent = (w * 64 + lane) | (tb << TB_SH);
+                }
+                return tb;
+            };
+            auto put_entry = [&](const uint32_t pos, const uint32_t ent) {
+                if constexpr (KL32) s_klist32[pos] = ent;
+                else s_klist[pos] = (uint16_t)ent;
+            };
+            if constexpr (TYPED) {
+                // count per class first, scatter second (two passes over the key words): each segment in
+                // ascending slot order.  A restricted SEND, or a SEND beside ECHOs / READYs, is general.
+                auto slot_class = [&](const uint32_t tb, const bool restr) -> uint32_t {
+                    return tb == TB_E ? 1u : tb == TB_R ? 2u : (tb == TB_S && !restr) ? 3u
+                                                              : (BRC_TYPED_ER && tb == (TB_E | TB_R)) ? 4u : 0u;
+                };
+                constexpr uint32_t LCT = SPEC ? BRC_LCHUNK_SPEC : LCHUNK;
+#pragma unroll
+                for (int c = 0; c < TCLS; ++c) scnt[c] = 0;
+                for (uint32_t w = 0; w < nkw; ++w) {
+                    uint32_t ent;
+                    bool restr;
+                    const uint32_t tb = slot_entry(w, ent, restr), cl = slot_class(tb, restr);
+#ifdef BRC_STAMPS
+                    for (uint32_t v = 1; v < 8; ++v) BRC_KCOUNT_N(4 + v, (uint32_t)__popcll(__ballot(tb == v)));
+#endif
+                    Unrolled<TCLS>::run([&](auto ci) {
+                        constexpr int c = decltype(ci)::value;
+                        scnt[c] += (uint32_t)__popcll(__ballot(tb != 0 && cl == (uint32_t)c));
+                    });
+                }
+                sbase[0] = 0;
+#pragma unroll
+                for (int c = 0; c < TCLS; ++c) sbase[c + 1] = sbase[c] + ((scnt[c] + LCT - 1u) & ~(LCT - 1u));
+                uint32_t spos[TCLS];
+#pragma unroll
+                for (int c = 0; c < TCLS; ++c) spos[c] = sbase[c];
+                for (uint32_t w = 0; w < nkw; ++w) {
+                    uint32_t ent;
+                    bool restr;
+                    const uint32_t tb = slot_entry(w, ent, restr), cl = slot_class(tb, restr);
+                    Unrolled<TCLS>::run([&](auto ci) {
+                        constexpr int c = decltype(ci)::value;
+                        const bool in = tb != 0 && cl == (uint32_t)c;
+                        const uint64_t bits = __ballot(in);
+                        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bits >> 32),
+                                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)bits, 0u));
+                        if (in) put_entry(spos[c] + below, ent);
+                        spos[c] += (uint32_t)__popcll(bits);
+                    });
+                }
+                // segment padding -> the trash row (fewer than a chunk per class)
+                Unrolled<TCLS>::run([&](auto ci) {
+                    constexpr int c = decltype(ci)::value;
+                    if (spos[c] + lane < sbase[c + 1]) put_entry(spos[c] + lane, NK);
+                    nk_lean += scnt[c];
+                });
+                nkeys = sbase[TCLS];
+            } else {
+            for (uint32_t w = 0; w < nkw; ++w) {
+                uint32_t ent;
+                bool restr;
+                const uint32_t tb = slot_entry(w, ent, restr);
                 const uint64_t bits = __ballot(tb != 0);
                 const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bits >> 32),
                                                                  __builtin_amdgcn_mbcnt_lo((uint32_t)bits, 0u));
-                if (tb != 0) {
-                    if constexpr (KL32) {
-                        const uint32_t sx = (tb & TB_S) ? (((m_sender(m) & 63u) << KL_SND_SH) | (((dt - 1u) & 15u) << KL_DT_SH) |
-                                                           ((m & M_RESTRICTED) ? KL_RESTR : 0u)) : 0u;
-                        s_klist32[nkeys + below] = (w * 64 + lane) | (tb << TB_SH) | sx;
-                    } else {
-                        s_klist[nkeys + below] = (uint16_t)((w * 64 + lane) | (tb << TB_SH));
-                    }
-                }
+#ifdef BRC_STAMPS
+                for (uint32_t v = 1; v < 8; ++v) BRC_KCOUNT_N(4 + v, (uint32_t)__popcll(__ballot(tb == v)));
+#endif
+                if (tb != 0) put_entry(nkeys + below, ent);
                 nkeys += (uint32_t)__popcll(bits);
+            }
             }
         } else if constexpr (PSEG) {
             // one key list per instance (segment): the segment's lanes list its marked slots, NPAD bits
@@ -1297,7 +1382,8 @@ void brc_step(const Params* __restrict__ pp) {
             if constexpr (KL32) s_klist32[nkeys + lane] = NK;
             else s_klist[nkeys + lane] = (uint16_t)NK;
         }
-        if constexpr (LEAN) nk_lean += nkeys;
+        if constexpr (LEAN && !TYPED) nk_lean += nkeys;    // (TYPED: the real entries, counted per class above)
+        (void)sbase; (void)scnt;
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         BRC_STAMP(0);
         // p < nkeys + CHUNK: padded list.  The key ids stay in SGPRs with the words they address,
@@ -1353,17 +1439,25 @@ void brc_step(const Params* __restrict__ pp) {
         };
         // mk_a / mk_v (NLR): this lane's ring mark for the pair (LDS word, bit; mk_a = NOKEY: none), issued
         // by the caller after the next chunk's key ids are read, so that read never waits for the mark
-        auto process_pair = [&](const uint32_t (&ent)[2], const uint64_t (&m)[2], const uint32_t (&lo)[2],
+        // tc = IC<TBC>: TBC >= 0 (TYPED) is the type bits of BOTH keys as a compile-time constant -- every branch
+        // on the types folds, a stage the class lacks leaves no instruction, and a padding key (the trash row:
+        // never sent, so no ECHO / READY arrival) changes nothing; TBC = -1 reads the bits from the entries
+        auto process_pair = [&](auto tc, const uint32_t (&ent)[2], const uint64_t (&m)[2], const uint32_t (&lo)[2],
                                 uint32_t (&nw)[2], bool (&wr)[2], uint32_t& mk_a, uint64_t& mk_v) {
+            constexpr int TBC = decltype(tc)::value;
             uint32_t k[2], tb[2], tE[2], tR[2], ea[2] = {0u, 0u}, ra[2] = {0u, 0u}, sa[2] = {0u, 0u};
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                k[i] = ent[i] & TB_KEY; tb[i] = (ent[i] >> TB_SH) & 7u;
+                k[i] = ent[i] & TB_KEY; tb[i] = TBC >= 0 ? (uint32_t)TBC : (ent[i] >> TB_SH) & 7u;
                 // lanes that are not real replicas and Byzantine lanes never update their cells here, so
                 // their words keep the fresh row's "never sent" unless an injection sent for them
                 tE[i] = (lo[i] >> C32_OE_SH) & 127u; tR[i] = lo[i] >> C32_OR_SH;   // offsets: SENT ECHO / READY
             }
             BRC_KCOUNT(0);
+#ifdef BRC_STAMPS
+            if (k[1] == NK) BRC_KCOUNT(13);
+            else if (((ent[0] ^ ent[1]) >> TB_SH) & 7u) BRC_KCOUNT(12);
+#endif
             // a type that cannot land on one key of the pair counts zero there: exact either way.
             // BRC_BRANCHLESS: ECHO and READY are always evaluated (a stage without arrivals is the
             // identity), so a pair is one basic block the scheduler can interleave
@@ -1390,7 +1484,8 @@ void brc_step(const Params* __restrict__ pp) {
                         const uint64_t mi = KL32 ? 0ull : uni64(m[i]);
                         const uint32_t dt = KL32 ? ((ent[i] >> KL_DT_SH) & 15u) + 1u : t - m_tsend(mi);
                         const uint32_t snd = KL32 ? (ent[i] >> KL_SND_SH) & 63u : m_sender(mi);
-                        const bool restr = KL32 ? (ent[i] & KL_RESTR) != 0 : (mi & M_RESTRICTED) != 0;
+                        // (a typed class holds no restricted SEND)
+                        const bool restr = TBC < 0 && (KL32 ? (ent[i] & KL_RESTR) != 0 : (mi & M_RESTRICTED) != 0);
                         bool hit;
                         if constexpr (NLR != 0) {
                             hit = (((RL0 >> snd) & 1) != 0) == (dt == dly0);
@@ -1399,6 +1494,8 @@ void brc_step(const Params* __restrict__ pp) {
                             hit = (s_L[sj * 64 + lane] >> snd) & 1;
                         }
                         uint64_t hm = __ballot(hit) & hon_mask;
+                        // the SEND class's padding key (the second of a segment's last pair) holds no SEND
+                        if (TBC >= 0 && i == 1 && k[i] == NK) hm = 0;
                         if (restr) hm &= __ballot((gp(P.kdst)[inst * NK + k[i]] >> d) & 1ull);
                         sa[i] = lane_in(hm) ? 1u : 0u;
                     }
@@ -1821,7 +1918,9 @@ void brc_step(const Params* __restrict__ pp) {
                 w[c] = cell(kk[c]);
                 __builtin_amdgcn_sched_barrier(0);
             });
-            for (uint32_t p = 0; p < nkeys; p += LC) {
+            // one chunk: list entries p .. p + LC - 1 of a segment whose real entries end at rend (tc: the segment's
+            // class, process_pair); the list ends at nkeys, a multiple of LC when TYPED
+            auto chunk = [&](auto tc, const uint32_t p, const uint32_t rend) {
                 uint64_t mm[LC];
                 Unrolled<LC>::run([&](auto ci) {
                     constexpr int c = decltype(ci)::value;
@@ -1854,7 +1953,7 @@ void brc_step(const Params* __restrict__ pp) {
                     bool wr[2] = {false, false};
                     uint32_t mk_a = NOKEY;
                     uint64_t mk_v = 0;
-                    if (p + c < nkeys) process_pair(ent, mp, lo, nw, wr, mk_a, mk_v);
+                    if (p + c < rend) process_pair(tc, ent, mp, lo, nw, wr, mk_a, mk_v);
                     cst_if(kk[c] & TB_KEY, nw[0], wr[0]);
                     cst_if(kk[c + 1] & TB_KEY, nw[1], wr[1]);
                     // refill (none after the last chunk: no load is left in flight past the loop, so the
@@ -1875,6 +1974,18 @@ void brc_step(const Params* __restrict__ pp) {
                     }
                     if (mk_a != NOKEY) atomicOr((unsigned long long*)&s_act[mk_a], mk_v);
                 });
+            };
+            if constexpr (TYPED) {
+                // one loop per class over its segment, the cell pipeline running on across segment boundaries
+                // (a segment is whole chunks, so every loop issues the same order of stores and loads)
+                uint32_t p = 0;
+                Unrolled<TCLS>::run([&](auto ci) {
+                    constexpr int c = decltype(ci)::value;
+                    const uint32_t rend = sbase[c] + scnt[c];
+                    for (; p < sbase[c + 1]; p += LC) chunk(IC<tcls_tb(c)>{}, p, rend);
+                });
+            } else {
+                for (uint32_t p = 0; p < nkeys; p += LC) chunk(IC<-1>{}, p, nkeys);
             }
         } else {
             // Record pre-pass (keys SENT again, a Byzantine replica's ECHO / READY to a subset of the peers:
@@ -2196,7 +2307,7 @@ void brc_step(const Params* __restrict__ pp) {
 
 #ifdef BRC_STAMPS
     if (lane == 0) for (int i = 0; i < 8; ++i) atomicAdd(&brc_stamps[i], (unsigned long long)stamp_acc[i]);
-    if (lane == 0) for (int i = 0; i < 4; ++i) atomicAdd(&brc_stamps[8 + i], (unsigned long long)kcount[i]);
+    if (lane == 0) for (int i = 0; i < 16; ++i) atomicAdd(&brc_stamps[8 + i], (unsigned long long)kcount[i]);
 #endif
 #undef BRC_STAMP
     // ---- write back

@@ -26,7 +26,7 @@ else:
     kw = {k: v for k, v in kw.items() if k != "kernel"}
     eng = Engine(instances=inst, **kw)
 lib = ctypes.CDLL(os.environ["BRC_LIB"])
-out = (ctypes.c_ulonglong * 12)()
+out = (ctypes.c_ulonglong * 24)()
 dbg = lib.brc_dbg_stamps_life if life else lib.brc_dbg_stamps16 if eng.n <= 16 else lib.brc_dbg_stamps256 if eng.n > 128 else lib.brc_dbg_stamps   # per unit
 eng.reset(); eng.run()
 dbg(out)
@@ -42,4 +42,11 @@ for nm, v in zip(names, out[:8]):
 kn = ["key-steps processed", "  no arrivals", "  only delivered cells", "  updated"]
 for nm, v in zip(kn if not (wide or life) else [], out[8:]):
     print("%-24s %.4g  (%.1f %%)" % (nm, v, 100.0 * v / max(1, out[8])))
+# lean key-list entries by the message types landing on the key (TB_S = 1, TB_E = 2, TB_R = 4) and pair mix
+if not (wide or life) and sum(out[12:20]):
+    ent = sum(out[13:20])
+    for tb in range(1, 8):
+        nm = "+".join(n for bit, n in ((1, "S"), (2, "E"), (4, "R")) if tb & bit)
+        print("entries %-16s %.4g  (%.1f %%)" % (nm, out[12 + tb], 100.0 * out[12 + tb] / max(1, ent)))
+    print("pairs: mixed types %.4g, padded %.4g of %.4g" % (out[20], out[21], out[8]))
 print("kernel ms %.2f" % eng.last_kernel_ms())
