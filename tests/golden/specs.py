@@ -122,6 +122,34 @@ def equivocation_actions(n, byzantine, nv=2, t_send=0, t_er=1):
     return acts
 
 
+def variant_actions(n, byzantine, nv, split="even", t_send=0, t_er=1):
+    """equivocation_actions over all nv key variants of an origin: each Byzantine replica b declares the keys
+    kp = b * nv + v (v < nv, s = 0) with value ids (1 + v) % 4 (1, 2, 3, 0: distinct, and ids every kernel takes),
+    SENDs them to disjoint destination sets, then ECHOes and READYs each of them to everyone.
+    split "even": destination d gets variant d % nv (nv = 2: exactly equivocation_actions).
+    split "skewed": variants 1 .. nv - 1 go to one honest destination each (rotating with the origin), variant 0
+    to every other destination, so variant 0 can reach its quorums and the others leave partial counts."""
+    assert nv in (2, 4) and split in ("even", "skewed")
+    allm = (1 << n) - 1
+    honest = [d for d in range(n) if d not in byzantine]
+    assert len(honest) >= nv - 1
+    acts = []
+    for i, b in enumerate(byzantine):
+        if split == "even":
+            dst = [sum(1 << d for d in range(v, n, nv)) for v in range(nv)]
+        else:
+            dst = [0] + [1 << honest[(i * (nv - 1) + v - 1) % len(honest)] for v in range(1, nv)]
+            dst[0] = allm & ~sum(dst)
+        for v in range(nv):
+            acts.append(dict(t=t_send, kind="byz_key", kp=b * nv + v, s=0, value=(1 + v) % 4))
+        for v in range(nv):
+            acts.append(dict(t=t_send, kind="byz", src=b, type=SEND, kp=b * nv + v, s=0, dst=dst[v]))
+        for v in range(nv):
+            acts.append(dict(t=t_er, kind="byz", src=b, type=ECHO, kp=b * nv + v, s=0, dst=allm))
+            acts.append(dict(t=t_er, kind="byz", src=b, type=READY, kp=b * nv + v, s=0, dst=allm))
+    return acts
+
+
 def deliver_actions(n, seed, count=None, nval=4):
     """Direct deliver() calls: replica `node` is handed host `kp`'s message with value id `value`
     (0 .. nval-1) at step t (an action: after step t's messages)."""
@@ -305,6 +333,16 @@ def scenario_groups():
     G["conn_cons_byz_n16"] = [cons_spec(16, 5, 0x5EED0003, m, d, g, round_cap=1, byzantine=list(range(11, 16)), nv=2,
                                         extra=equivocation_actions(16, list(range(11, 16))), peer_mode="connection")
                               for (m, d) in ((1, 4), (2, 4)) for g in range(2)]
+    # four key variants per origin (variant_actions): three Byzantine replicas, both splits.  With the skewed split
+    # variant 0 of each reaches the echo quorum (13 honest - 3 + the origin's own ECHO = 11 > (n + f) / 2)
+    byz4 = [13, 14, 15]
+    for pm, pre in (("sender", ""), ("connection", "conn_")):
+        # (key_window: the engine's; its default 8 // nv = 2 is less than the phase indices one round keeps live)
+        G[pre + "cons_equivocate4_n16"] = [dict(cons_spec(16, 5, 0x5EED0043, m, d, g, round_cap=1, byzantine=byz4, nv=4,
+                                                          extra=variant_actions(16, byz4, 4, split), peer_mode=pm),
+                                                key_window=8)
+                                           for (m, d) in ((1, 4), (2, 4), (0, 1))
+                                           for g, split in enumerate(("even", "skewed"))]
     # ByzantineRandomizedConsensus.deliver(message) called directly (core/byzantinerandomizedconsensus.py:53):
     # extra values from chosen hosts, some before the replica's own proposal (phase 0: counted only)
     G["cons_deliver_n6"] = [cons_spec(6, 1, 0xDE10, m, d, g, round_cap=2, starts=[0, 0, 0, 3, 0, 6],

@@ -89,3 +89,30 @@ def test_create_failure_reason_is_reported():
     bad = L.Config(n=4, f=1, instances=1, delay_max=1, delay_const=1, key_window=3, variants=1)
     assert lib.brc_create(ctypes.byref(bad), ctypes.byref(h)) == L.E_INVALID
     assert b"invalid configuration" in lib.brc_last_error(None)
+
+
+def test_key_layouts_outside_the_kernels_limits_are_refused():
+    """key_window x variants beyond what a kernel family addresses (brc_create's first check, before any device
+    call): Q * NV <= 8 under SPEC and at n > 64, one variant under SPEC at n > 64.  The same shape with a layout
+    inside the limit is no BRC_E_INVALID (without a device it fails later, with BRC_E_HIP)."""
+    lib = L.load()
+    base = dict(instances=2, protocol=L.PROTO_CONSENSUS, delay_model=L.DELAY_SLOWSET, delay_max=4, delay_const=1,
+                round_cap=1, step_cap=4000, proposals=L.PROPOSALS_PHILOX)
+    refused = [dict(n=16, f=5, mode=L.MODE_SPEC, key_window=4, variants=4),
+               dict(n=70, f=23, mode=L.MODE_SPEC, key_window=2, variants=2),
+               dict(n=70, f=23, mode=L.MODE_REFERENCE, key_window=4, variants=4),
+               dict(n=70, f=23, mode=L.MODE_REFERENCE, key_window=8, variants=2)]
+    taken = [dict(n=16, f=5, mode=L.MODE_SPEC, key_window=2, variants=4),
+             dict(n=70, f=23, mode=L.MODE_SPEC, key_window=2, variants=1),
+             dict(n=70, f=23, mode=L.MODE_REFERENCE, key_window=2, variants=4),
+             dict(n=70, f=23, mode=L.MODE_REFERENCE, key_window=4, variants=2)]
+    for kw in refused:
+        h = ctypes.c_void_p()
+        assert lib.brc_create(ctypes.byref(L.Config(**dict(base, **kw))), ctypes.byref(h)) == L.E_INVALID, kw
+        assert not h.value and b"invalid configuration" in lib.brc_last_error(None)
+    for kw in taken:
+        h = ctypes.c_void_p()
+        rc = lib.brc_create(ctypes.byref(L.Config(**dict(base, **kw))), ctypes.byref(h))
+        assert rc != L.E_INVALID, (kw, lib.brc_last_error(None))
+        if rc == L.OK:
+            lib.brc_destroy(h)

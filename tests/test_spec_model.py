@@ -22,7 +22,9 @@ def _check(sp):
     return got
 
 
-def _random_specs(seed, count):
+def _random_specs(seed, count, variants=False):
+    """variants: Byzantine runs draw nv from {2, 4} and a split of specs.variant_actions (every variant of an origin in
+    use); the draws of the existing chunks are unchanged without it."""
     rng = random.Random(seed)
     out = []
     for i in range(count):
@@ -38,12 +40,20 @@ def _random_specs(seed, count):
         else:
             byz = rng.sample(range(n), rng.randint(0, f))
             extra = []
-            if byz and rng.random() < 0.5:
+            nv = 2
+            if variants and f and not byz:
+                byz = rng.sample(range(n), rng.randint(1, f))
+            if variants and byz:
+                nv = rng.choice([2, 4])
+                if len(byz) <= n - nv:
+                    extra = S.variant_actions(n, byz, nv, rng.choice(["even", "skewed"]))
+                    window = 2 if nv == 4 else rng.choice([2, 4])       # the engine's limit: Q * NV <= 8 under SPEC
+            elif byz and rng.random() < 0.5:
                 extra = S.equivocation_actions(n, byz)
             starts = None if rng.random() < 0.6 else [rng.choice([0, 0, rng.randint(1, 8)]) for _ in range(n)]
             sp = S.spec_cons_spec(n, f, rng.getrandbits(40), model, dmax, g, round_cap=rng.randint(1, 4),
                                   window=window, coin_seed=rng.getrandbits(40), byzantine=byz,
-                                  nv=2 if extra else 1, extra=extra, starts=starts, step_cap=3000)
+                                  nv=nv if extra else 1, extra=extra, starts=starts, step_cap=3000)
         sp["name"] = "specfuzz/%d" % i
         out.append(sp)
     return out
@@ -52,6 +62,16 @@ def _random_specs(seed, count):
 @pytest.mark.parametrize("chunk", range(4))
 def test_oracle_spec_matches_model(chunk):
     for sp in _random_specs(1000 + chunk, 40):
+        _check(sp)
+
+
+@pytest.mark.parametrize("chunk", range(2))
+def test_oracle_spec_matches_model_with_every_variant(chunk):
+    """Two and four key variants per origin (specs.variant_actions, both splits): the `seen` host masks of
+    spec_deliver are indexed by the host kp // nv."""
+    specs = _random_specs(2000 + chunk, 60, variants=True)
+    assert sum(sp["nv"] == 4 for sp in specs) >= 5 and sum(sp["nv"] == 2 for sp in specs) >= 5
+    for sp in specs:
         _check(sp)
 
 
