@@ -193,9 +193,11 @@ struct Engine {
     std::unordered_map<uint64_t, uint32_t> key_recs;    // instance << 32 | kp << 16 | s -> allocating records
     std::unordered_map<uint64_t, uint32_t> slot_extra;  // instance << 32 | slot -> the slot's count for gen_extra
     std::unordered_map<uint64_t, uint32_t> prop_recs;   // instance << 32 | node -> PROPOSE records
-    // injected SENDs per key (instance << 32 | kp << 16 | s): how many, and each sender's destinations
+    // injected SENDs per key (instance << 32 | kp << 16 | s): how many, and each sender's destinations (all four
+    // words: the wide kernels' extra SENDs drop a node's used links over bw words)
+    struct SendDst { uint32_t node; uint64_t dst[4]; };
     std::unordered_map<uint64_t, uint32_t> send_count;
-    std::unordered_map<uint64_t, std::vector<std::pair<uint32_t, uint64_t>>> send_dst;
+    std::unordered_map<uint64_t, std::vector<SendDst>> send_dst;
     // type: 0 = an extra SEND; BRC_ECHO / BRC_READY = a Byzantine replica's message to a subset of the peers
     struct XRec { uint32_t k, t, seg, type; uint64_t smask, dst; };
     std::unordered_map<uint64_t, std::vector<XRec>> xrec;   // item -> records in flight (P.xsend)
@@ -205,7 +207,7 @@ struct Engine {
     std::unordered_map<uint64_t, uint64_t> msg_used;
     std::unordered_map<uint64_t, bool> msg_rec;
     // the same on the wide kernels under BRC_FLAG_WIDE_RECORDS (brc_step_wide.h REC): one instance per item, one
-    // sender per record, destination and used-link sets of bw words (four kept)
+    // sender per record, destination and used-link sets of bw words (four kept).  type 0: an extra SEND
     bool wide_rec = false;
     struct WRec { uint32_t k, t, type, node; uint64_t dst[4]; };
     struct WUsed { uint64_t w[4] = {0, 0, 0, 0}; bool rec = false; };
@@ -680,7 +682,7 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
     std::vector<InjDev> staged;
     std::vector<uint64_t> staged_item;
     std::unordered_map<uint64_t, uint32_t> new_count;                                   // this batch's SENDs
-    std::unordered_map<uint64_t, std::vector<std::pair<uint32_t, uint64_t>>> new_dst;
+    std::unordered_map<uint64_t, std::vector<Engine::SendDst>> new_dst;
     std::unordered_map<uint64_t, uint64_t> new_used;                                    // this batch's ECHO / READY links
     std::unordered_map<uint64_t, bool> new_rec;
     // restricted ECHO / READY: the non-lean narrow step kernels with sender peers (brc_step.h record pre-pass)
@@ -777,35 +779,43 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
                 }
             } else if (x.kind == BRC_INJ_SEND) {
                 // a second SEND of a key (another origin or the same, one payload string SENT again):
-                // an extra-SEND record on the non-lean step kernels; the lean and wide kernels model
-                // one SEND per key
+                // an extra-SEND record on the non-lean narrow step kernels and on the wide kernels of an engine
+                // created with BRC_FLAG_WIDE_RECORDS; the lean and the flagless wide kernels model one SEND per key
                 const uint64_t k64 = (x.instance << 32) | (uint64_t)(x.kp * 0x10000u + x.s);
                 auto it0 = e->send_count.find(k64);
                 auto it1 = new_count.find(k64);
                 const uint32_t before = (it0 != e->send_count.end() ? it0->second : 0u) +
                                         (it1 != new_count.end() ? it1->second : 0u);
-                if ((e->compact || e->wide) && before) {
-                    e->err = "a key can be SENT only once on this kernel (n in 33..64 with sender peers, or n > 64)";
+                const bool one_send = e->compact || (e->wide && !e->wide_rec);
+                if (one_send && before) {
+                    e->err = "a key can be SENT only once on this kernel (n in 33..64 with sender peers, or n > 64 "
+                             "without BRC_FLAG_WIDE_RECORDS)";
                     return BRC_E_UNSUPPORTED;
                 }
                 ++new_count[k64];
                 // this node's earlier SENDs of the key (this batch included): r.type = 1 marks a repeat
                 // (brc_step.h: a COPY event with connection peers); sender peers carry a repeated
                 // message on a link no further (the links it used are dropped from the record)
-                uint64_t prev = 0;
+                uint64_t prev[4] = {0, 0, 0, 0};
                 bool had = false;
                 for (const auto* mp : {&e->send_dst, &new_dst}) {
                     auto it = mp->find(k64);
                     if (it != mp->end())
                         for (const auto& q : it->second)
-                            if (q.first == x.node) { prev |= q.second; had = true; }
+                            if (q.node == x.node) {
+                                for (int w = 0; w < 4; ++w) prev[w] |= q.dst[w];
+                                had = true;
+                            }
                 }
-                new_dst[k64].push_back({x.node, r.dst});
+                new_dst[k64].push_back(Engine::SendDst{x.node, {r.dst, r.dst_hi[0], r.dst_hi[1], r.dst_hi[2]}});
                 // a key SENT before (by any node): an extra-SEND record (bit 1), bit 0 = this node's repeat
-                const bool again = !(e->compact || e->wide) && before > 0;
+                const bool again = !one_send && before > 0;
                 r.type = (again ? 2 : 0) | (had ? 1 : 0);
-                if (c.peer_mode == BRC_PEER_SENDER) r.dst &= ~prev;
-                drop = had && r.dst == 0;
+                if (c.peer_mode == BRC_PEER_SENDER) {
+                    r.dst &= ~prev[0];
+                    for (int w = 0; w < 3; ++w) r.dst_hi[w] &= ~prev[w + 1];
+                }
+                drop = had && !(r.dst | r.dst_hi[0] | r.dst_hi[1] | r.dst_hi[2]);
             }
         } else {
             e->err = "unknown injection kind";
@@ -843,7 +853,9 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
     for (size_t i = 0; e->wide_rec && i < staged.size(); ++i) {
         const InjDev& r = staged[i];
         const uint64_t dst[4] = {r.dst, r.dst_hi[0], r.dst_hi[1], r.dst_hi[2]};
-        if (r.kind != BRC_INJ_MSG || !r.restricted || !any4(dst)) continue;   // no link left: no record
+        const bool xsend = r.kind == BRC_INJ_SEND && (r.type & 2);
+        const bool xmsg = r.kind == BRC_INJ_MSG && r.restricted;
+        if ((!xsend && !xmsg) || !any4(dst)) continue;   // no link left: no record
         const uint64_t item = staged_item[i];
         if (!wnew.count(item)) {
             std::vector<Engine::WRec> v0;
@@ -854,10 +866,10 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
         }
         auto& v = wnew[item];
         if (v.size() >= XSEND_MAX) {
-            e->err = "more than " + std::to_string(XSEND_MAX) + " restricted ECHO / READY records in flight in one instance";
+            e->err = "more than " + std::to_string(XSEND_MAX) + " extra-SEND / restricted ECHO / READY records in flight in one instance";
             return BRC_E_UNSUPPORTED;
         }
-        v.push_back(Engine::WRec{r.slot, r.t, r.type, r.node, {dst[0], dst[1], dst[2], dst[3]}});
+        v.push_back(Engine::WRec{r.slot, r.t, xsend ? 0u : (uint32_t)r.type, r.node, {dst[0], dst[1], dst[2], dst[3]}});
     }
     for (size_t i = 0; !e->wide_rec && i < staged.size(); ++i) {
         const InjDev& r = staged[i];

@@ -161,8 +161,9 @@ constexpr uint32_t XSEND_MAX = 16;
 // (0: an extra SEND; BRC_ECHO / BRC_READY: a restricted message)
 constexpr uint32_t XS_TYPE_SH = 48;
 // Wide kernels under BRC_FLAG_WIDE_RECORDS (brc_step_wide.h REC): the same table per instance holds restricted
-// ECHO / READY records only, WREC_W words each -- the first word as above with the one sender at WREC_NODE_SH (no
-// segment: one instance per workgroup), then the destination set's four words (words past NPAD / 64 are zero)
+// ECHO / READY records and extra SENDs (type 0: a SEND of a key SENT before), WREC_W words each -- the first word as
+// above with the one sender at WREC_NODE_SH (no segment: one instance per workgroup), then the destination set's four
+// words (words past NPAD / 64 are zero)
 constexpr uint32_t WREC_W = 5;
 constexpr uint32_t WREC_NODE_SH = 56;
 

@@ -64,7 +64,9 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t x) {
 // REC (BRC_FLAG_WIDE_RECORDS): a Byzantine replica's ECHO / READY to a subset of the peers (include/brc.h,
 // "Restricted ECHO / READY").  Such a message has no cell representation -- the sender's cell holds one send step
 // for all its links -- so brc_inject keeps it as a record of the instance's table (P.xsend: WREC_W words each, P.xsn
-// in use) and each receiver lane adds its own hits to the ballot-derived counts.  false: none of this is compiled.
+// in use) and each receiver lane adds its own hits to the ballot-derived counts.  An extra SEND of a key (a payload
+// SENT by a second node, or again) is a record of the same table with message type 0: the slot keeps the first SEND,
+// and a cell's SEND arrivals of one step become a count.  false: none of this is compiled.
 template <int NPAD, int DM, bool EV, int MODE, int WV = 0, bool REC = false>
 __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ? BRC_WIDE_WAVES16 : BRC_WIDE_WAVES)) void brc_step_wide(const Params* __restrict__ pp) {
     const Params& P = *pp;
@@ -491,13 +493,39 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
                 const bool is_send = r.kind == BRC_INJ_SEND;
                 // restricted SEND (equivocation): this wave's word of the destination set, kept per
                 // key in kdst for the arrival test; each wave writes and reads only its own word
-                const bool restricted = is_send && r.restricted;
-                const uint64_t dw = restricted ? gp((const uint64_t*)(P.inj + inj_off + inj_pos - 1))[2 + wid] : ~0ull;
+                // REC: a SEND of a key already SENT (another node's, or this node's again; r.type bit 1, brc_inject).
+                // The slot, its sender, send step, value and kdst stay the first SEND's; brc_inject has put the links
+                // this one travels on (always its own words, restricted or not) in the instance's table as a type-0
+                // record, which process() lands
+                const bool xs = REC && is_send && (r.type & 2u);
+                const bool restricted = is_send && r.restricted && !xs;
+                const uint64_t dw = (restricted || xs) ? gp((const uint64_t*)(P.inj + inj_off + inj_pos - 1))[2 + wid] : ~0ull;
                 uint32_t myset = 0;
                 if (is_send && mine && honest && ((dw >> lane) & 1ull)) myset = 1u << (link_delay(r.node) - 1);
                 if (restricted && mine && lane == 0) gp(P.kdst)[(inst * NK + r.slot) * NW + wid] = dw;
                 const uint32_t os = block_or(myset);
-                if (mine) {
+                if (xs) {
+                    if (mine) {
+                        const uint32_t k = r.slot;
+                        if (d == 0) {
+                            const uint64_t m = s_meta[k];
+                            if (m_s1(m) != r.s + 1u || m_tsend(m) == NEVER) {
+                                badinj = true;                   // the key is not the SENT one brc_inject saw
+                            } else {
+                                if (t + hibit(os) > m_tquiet(m)) s_meta[k] = m_with_tquiet(m, t + hibit(os));
+                                mark_lane(k, os);
+                                const gptr_t<const uint64_t> rw = gp((const uint64_t*)(P.inj + inj_off + inj_pos - 1));
+                                uint32_t nd = 0;                 // links used, Byzantine destinations included
+#pragma unroll
+                                for (int w = 0; w < NW; ++w) nd += (uint32_t)__popcll(rw[2 + w]);
+                                st_msgs += nd;
+                                // a node's first SEND of the key is a SEND event, its repeat none (sender peers)
+                                if (!(r.type & 1u)) log_ev(BRC_EV_SEND, r.node, BRC_SEND, (k >> qsh), r.s, m_value(m));
+                            }
+                        }
+                        q_until = max(q_until, t + hibit(os));
+                    }
+                } else if (mine) {
                     const uint32_t k = r.slot;
                     if (d == 0) {
                         uint64_t m = s_meta[k];
@@ -860,9 +888,10 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
                     }
                 }
             }
+            uint32_t xsa = 0;                                    // REC: extra SENDs of this key landing here now
             if constexpr (REC) {
-                // restricted ECHO / READY records of this key: receiver d counts the ones whose destination set holds
-                // it and whose link delay node -> d has passed exactly now (lane-local: no exchange)
+                // restricted ECHO / READY records and extra SENDs (type 0) of this key: receiver d counts the ones whose
+                // destination set holds it and whose link delay node -> d has passed exactly now (lane-local: no exchange)
                 for (uint32_t ra_ = rec_act; ra_; ra_ &= ra_ - 1) {
                     const gptr_t<const uint64_t> rp = recs + ((uint32_t)__ffs(ra_) - 1u) * WREC_W;
                     const uint64_t w0 = uni64(rp[0]);
@@ -870,8 +899,10 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
                     const uint64_t dw = rp[1 + wid];
                     const bool hit = ((dw >> lane) & 1ull) &&
                                      ((uint32_t)(w0 >> 16) & 0xFFFFu) + link_delay((uint32_t)(w0 >> WREC_NODE_SH) & 0xFFu) == tsl;
-                    if (((uint32_t)(w0 >> XS_TYPE_SH) & 3u) == BRC_ECHO) ea += hit ? 1u : 0u;
-                    else ra += hit ? 1u : 0u;
+                    const uint32_t ty = (uint32_t)(w0 >> XS_TYPE_SH) & 3u;       // workgroup-uniform
+                    if (ty == BRC_ECHO) ea += hit ? 1u : 0u;
+                    else if (ty == BRC_READY) ra += hit ? 1u : 0u;
+                    else xsa += hit ? 1u : 0u;
                 }
             }
             BRC_WSTAMP(3);
@@ -883,6 +914,12 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
                 bool hit = link_delay(m_sender(m)) == dt;
                 if (m & M_RESTRICTED) hit = hit && ((gp(P.kdst)[(inst * NK + k) * NW + wid] >> lane) & 1ull);
                 s_arr = honest && hit;
+            }
+            // SEND arrivals as a count: a first SEND and extra SENDs may land on one cell in one step
+            uint32_t sa = 0;
+            if constexpr (REC) {
+                sa = (s_arr ? 1u : 0u) + (honest ? xsa : 0u);
+                s_arr = sa != 0;
             }
             const bool has = kl && honest && (s_arr || ea || ra);
             st_loads += (kl && real) ? 1u : 0u;
@@ -918,7 +955,8 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
                 mycells[(size_t)k * (CW * NPAD)] = has ? nw : wd;
 #endif
             }
-            st_arr += has ? ea + ra + (s_arr ? 1u : 0u) : 0u;
+            if constexpr (REC) st_arr += has ? ea + ra + sa : 0u;
+            else st_arr += has ? ea + ra + (s_arr ? 1u : 0u) : 0u;
             st_cells += has ? 1u : 0u;
             st_msgs += ((es ? 1u : 0u) + (CONN ? n_ready : (rs ? 1u : 0u))) * n;
             st_del += dl ? 1u : 0u;

@@ -27,9 +27,12 @@ Deviations from the reference, all reported by exceptions and never silent:
   dicts are keyed by the payload string); the engine models it as one key with extra SENDs
   (brc_step.h extra-SEND records: up to 16 per wave item, shared by the instances packed into
   it) on clusters up to 64 nodes (33..64 nodes with sender peers run the narrow kernel's general
-  form for this, brc.h BRC_FLAG_GENERAL_KEYS); above 64 nodes a second origin raises
-  ``EngineError``.  A node that SENDs its own payload again with sender peers is a no-op
-  everywhere: the network drops a duplicate on every link (tests/golden/refharness.py).
+  form for this, brc.h BRC_FLAG_GENERAL_KEYS).  Above 64 nodes a broadcast cluster with sender
+  peers runs the wide kernels' record form (brc.h BRC_FLAG_WIDE_RECORDS: up to 16 records in
+  flight, shared with restricted ECHO / READY); with connection peers, and on best-effort
+  clusters above 32 nodes, a second SEND of a payload raises ``EngineError``.  A node that SENDs
+  its own payload again with sender peers is a no-op everywhere: the network drops a duplicate
+  on every link (tests/golden/refharness.py).
 * ``broadcast(type, m)`` takes SEND, ECHO and READY (the reference also puts other types on
   the wire, which its handler then ignores): other types raise ``EngineError``.
 * Peer addresses in ``peer_list`` without a constructed node in this process are silent
@@ -162,10 +165,11 @@ class Cluster:
         self.sent = set()          # keys SENT (a payload may be declared first by an ECHO / READY)
         # three-bit value ids on the narrow kernels that keep them (include/brc.h brc_injection.value)
         n = len(peers)
-        # the wide kernel (> 64 nodes): two-bit value ids, one SEND per key.  33..64 nodes with sender peers
-        # run the narrow kernel's general form (BRC_FLAG_GENERAL_KEYS), which keeps what n <= 32 keeps
-        self.lean_or_wide = n > 64
-        self.values = ValueTable(4 if self.lean_or_wide else 8)
+        # the wide kernel (> 64 nodes): two-bit value ids, and one SEND per key unless the engine keeps records
+        # (one_send).  33..64 nodes with sender peers run the narrow kernel's general form
+        # (BRC_FLAG_GENERAL_KEYS), which keeps what n <= 32 keeps
+        self.two_bit_ids = n > 64
+        self.values = ValueTable(4 if self.two_bit_ids else 8)
         self.engine = None
         self.seen_events = 0
         self.finished = False
@@ -205,7 +209,7 @@ class Cluster:
             if len(self.values.strings) > 4:
                 raise L.EngineError(L.E_UNSUPPORTED, "more than 3 distinct proposal values on %d nodes" % self.N)
             self.values.cap = 4
-            self.lean_or_wide = True
+            self.two_bit_ids = True
         self.nodes[i] = node
         return i
 
@@ -215,6 +219,18 @@ class Cluster:
     @property
     def mode(self):
         return "consensus" if self.cons else "brb"
+
+    @property
+    def wide_records(self):
+        """A broadcast cluster above 64 nodes with sender peers: its engine keeps extra SENDs of a key as
+        records (brc.h BRC_FLAG_WIDE_RECORDS; brc_create refuses the flag with connection peers)."""
+        return len(self.peers) > 64 and not self.beb and not self.cons and self.cfg["peer_mode"] == "sender"
+
+    @property
+    def one_send(self):
+        """The cluster's kernel models one SEND per key: the lean kernels (best-effort broadcast above 32
+        nodes) and the wide kernels without records."""
+        return (self.beb and len(self.peers) > 32) or (len(self.peers) > 64 and not self.wide_records)
 
     def pending_work(self):
         return not self.finished and bool(self.actions)
@@ -239,9 +255,9 @@ class Cluster:
         payload = str(payload)
         key = self._key_of(i, payload)
         sender_peers = self.beb or self.cfg["peer_mode"] == "sender"
-        if key[0] == i and key in self.sent and sender_peers and self.lean_or_wide:
+        if key[0] == i and key in self.sent and sender_peers and self.one_send:
             return            # the same node's repeat: a duplicate on every link, nothing travels
-        if (key[0] != i or key in self.sent) and self.lean_or_wide:
+        if (key[0] != i or key in self.sent) and self.one_send:
             raise L.EngineError(L.E_UNSUPPORTED, "payload %r SENT twice (one reference key) on a %d-node cluster "
                                 "with %s peers" % (payload, len(self.peers), self.cfg["peer_mode"]))
         self.sent.add(key)
@@ -296,7 +312,7 @@ class Cluster:
                              event_capacity=c["event_capacity"], instance_offset=c["instance_id"],
                              device=c["device"], mode=L.MODE_BEB if self.beb else L.MODE_REFERENCE,
                              peer_mode=L.PEER_SENDER if self.beb else PEER_MODES[c["peer_mode"]],
-                             general_keys=not self.beb)
+                             general_keys=not self.beb, wide_records=self.wide_records)
 
     def _flush(self):
         if self.actions:

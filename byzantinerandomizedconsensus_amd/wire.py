@@ -125,7 +125,11 @@ class Codec:
         ``general_keys``) and on the wide kernels (n > 64, destination masks of up to 256 bits) of an
         engine created with ``wide_records``; connection peers, the lean kernels (n in 33..64 without
         the flag), the wide kernels without theirs and lifetime-kernel-only engines refuse it with
-        ``E_UNSUPPORTED`` (include/brc.h, "Restricted ECHO / READY")."""
+        ``E_UNSUPPORTED`` (include/brc.h, "Restricted ECHO / READY").
+
+        Two SENDs of one key (a payload SENT by a second node, or again) become two ``INJ_SEND`` records;
+        the second is an extra SEND where the engine takes one (n <= 32, ``general_keys`` at 33..64, and
+        ``wide_records`` above 64 with sender peers)."""
         from . import _lib as L
         groups, declared, out = {}, set(), []
         senders = {w[1] for w in wire}

@@ -115,8 +115,8 @@ typedef struct {
  * always have.  For the class API's single-instance clusters; the batched workloads keep the lean
  * kernels (4-B cells, 2-bit ids).
  * BRC_FLAG_WIDE_RECORDS (v8): at n > 64 with sender peers (any mode, either protocol), run the wide kernel's
- * instantiations that take restricted ECHO / READY records (below).  Opt-in: an engine without the flag launches
- * the kernels it always did and refuses such records; with it the 4-waves-per-SIMD instantiations are not used and
+ * instantiations that take records: restricted ECHO / READY (below) and extra SENDs of one key (brc_injection.dst_mask).
+ * Opt-in: an engine without the flag launches the kernels it always did and refuses such records; with it the 4-waves-per-SIMD instantiations are not used and
  * every step tests one more word, so a run without records is slightly slower.  With n <= 64 or
  * connection peers brc_create fails with BRC_E_INVALID and a reason. */
 enum { BRC_FLAG_GENERAL_KEYS = 1, BRC_FLAG_WIDE_RECORDS = 2 };
@@ -164,14 +164,22 @@ typedef struct {
     uint64_t dst_mask;        /* BRC_INJ_SEND / BRC_INJ_MSG destinations 0..63.  A second
                                  SEND of a key (another node, or the same again: one payload string
                                  SENT twice, one key in the reference) is an extra SEND on the
-                                 narrow kernels that keep 3-bit value ids (it must not precede the
-                                 key's first SEND); BRC_E_UNSUPPORTED on the others.  A BRC_INJ_MSG
+                                 narrow kernels that keep 3-bit value ids and, at n > 64 with sender
+                                 peers, on an engine created with BRC_FLAG_WIDE_RECORDS (value ids
+                                 stay 2 bits there).  It must not precede the key's first SEND
+                                 (BRC_BADINJ for its instance), travels on the links of its
+                                 destination set that its node has not used for a SEND of the key
+                                 (sender peers; with none left it is accepted and changes nothing)
+                                 and leaves the key's sender, send step, value and the first SEND's
+                                 destination set as they are.  BRC_E_UNSUPPORTED on the others: the
+                                 lean kernels, the wide kernels without the flag (connection peers
+                                 above 64 cannot have it), lifetime-only engines.  A BRC_INJ_MSG
                                  to a proper subset of the peers (restricted ECHO / READY, below) is
                                  a record of the same table.  The table holds up to 16 records
                                  (extra SENDs and restricted ECHOs / READYs together) in flight per
                                  wave item (64 / NPAD instances, NPAD = n rounded up to 4, 8, 16,
-                                 32, 64; n > 64 under BRC_FLAG_WIDE_RECORDS: per instance, restricted
-                                 ECHOs / READYs only); one more: BRC_E_UNSUPPORTED, nothing changed */
+                                 32, 64; n > 64 under BRC_FLAG_WIDE_RECORDS: per instance); one more:
+                                 BRC_E_UNSUPPORTED, nothing changed */
     uint64_t dst_mask_hi[3];  /* destinations 64..255 (n > 64), as byzantine_mask_hi */
 } brc_injection;
 
