@@ -209,6 +209,7 @@ struct Engine {
     // the same on the wide kernels under BRC_FLAG_WIDE_RECORDS (brc_step_wide.h REC): one instance per item, one
     // sender per record, destination and used-link sets of bw words (four kept).  type 0: an extra SEND
     bool wide_rec = false;
+    bool wide_val = false;                       // BRC_FLAG_WIDE_VALUES: the wide kernels with 3-bit value ids (V8)
     struct WRec { uint32_t k, t, type, node; uint64_t dst[4]; };
     struct WUsed { uint64_t w[4] = {0, 0, 0, 0}; bool rec = false; };
     std::unordered_map<uint64_t, std::vector<WRec>> wrec;   // instance -> records in flight (P.xsend)
@@ -272,8 +273,10 @@ static uint64_t gen_used(const Engine* e) {
     return gen_passes(e) * (e->gen_smax / e->cfg.key_window + 1) + e->gen_extra + 1;
 }
 
-static int launch_step(int npad, int dm, bool events, int mode, bool wv4, bool rec, uint32_t blocks, uint32_t lds,
+static int launch_step(int npad, int dm, bool events, int mode, bool wv4, bool rec, bool v8, uint32_t blocks, uint32_t lds,
                        hipStream_t st, const Params* P) {
+    if (v8) return npad == 128 ? launch_step_128v(dm, events, mode, blocks, lds, st, P)
+                               : launch_step_256v(dm, events, mode, blocks, lds, st, P);
     if (rec) return npad == 128 ? launch_step_128x(dm, events, mode, blocks, lds, st, P)
                                 : launch_step_256x(dm, events, mode, blocks, lds, st, P);
     switch (npad) {
@@ -451,7 +454,7 @@ int brc_create(const brc_config* cfg, void** out) {
         c.f >= c.n || (c.byz_pattern == BRC_BYZ_EQUIVOCATE && c.variants < 2) ||
         (c.byz_pattern != BRC_BYZ_NONE && c.byz_pattern != BRC_BYZ_EQUIVOCATE) ||
         c.proposals > BRC_PROPOSALS_LOADED || c.mode > BRC_MODE_BEB ||
-        (c.flags & ~(uint32_t)(BRC_FLAG_GENERAL_KEYS | BRC_FLAG_WIDE_RECORDS)) ||
+        (c.flags & ~(uint32_t)(BRC_FLAG_GENERAL_KEYS | BRC_FLAG_WIDE_RECORDS | BRC_FLAG_WIDE_VALUES)) ||
         // the general form at NPAD = 64 with sender peers is the reference protocol's (KMODE_XREF)
         ((c.flags & BRC_FLAG_GENERAL_KEYS) && c.n > 32 && c.n <= 64 && c.peer_mode == BRC_PEER_SENDER &&
          c.mode != BRC_MODE_REFERENCE) ||
@@ -465,6 +468,14 @@ int brc_create(const brc_config* cfg, void** out) {
                                    "ECHO / READY records without a flag (n <= 32, or BRC_FLAG_GENERAL_KEYS at n in 33..64)"
                                  : "BRC_FLAG_WIDE_RECORDS needs sender peers: with connection peers every message is a new "
                                    "peer, and the records count senders";
+        return BRC_E_INVALID;
+    }
+    if ((c.flags & BRC_FLAG_WIDE_VALUES) && (c.n <= 64 || c.peer_mode != BRC_PEER_SENDER || c.mode == BRC_MODE_SPEC)) {
+        g_create_err = c.n <= 64 ? "BRC_FLAG_WIDE_VALUES is for the wide kernels (n > 64): the narrow kernels keep 3-bit value "
+                                   "ids without it (n <= 32, connection peers, or BRC_FLAG_GENERAL_KEYS at n in 33..64)"
+                     : c.mode == BRC_MODE_SPEC ? "BRC_FLAG_WIDE_VALUES: not with BRC_MODE_SPEC, whose consensus is binary"
+                                               : "BRC_FLAG_WIDE_VALUES needs sender peers: the connection-peer wide kernels "
+                                                 "keep 2-bit value ids";
         return BRC_E_INVALID;
     }
     Engine* e = new Engine();
@@ -501,10 +512,13 @@ int brc_create(const brc_config* cfg, void** out) {
     // wide kernel at 4 waves per SIMD (128 VGPRs): DM <= 8 without delay-code planes in registers (constant /
     // slow-set delays), sender peers, and LDS for four workgroups per CU
     // BRC_FLAG_WIDE_RECORDS: the instantiations with the record path (3 waves per SIMD, or 2 at DM = 16, only)
-    e->wide_rec = e->wide && (c.flags & BRC_FLAG_WIDE_RECORDS);
+    // BRC_FLAG_WIDE_VALUES: 3-bit value ids (V8), instantiated in the record form only -- such an engine takes what
+    // a BRC_FLAG_WIDE_RECORDS engine takes, and the two flags together select the same kernels
+    e->wide_val = e->wide && (c.flags & BRC_FLAG_WIDE_VALUES);
+    e->wide_rec = e->wide && (c.flags & (BRC_FLAG_WIDE_RECORDS | BRC_FLAG_WIDE_VALUES));
     e->wide_wv4 = e->wide && e->dm <= 8 && !plane_model(c.delay_model) && c.peer_mode == BRC_PEER_SENDER &&
                   e->lds_bytes <= 40u * 1024u && !e->wide_rec;
-    e->nval = value_ids(!e->compact && !e->wide);
+    e->nval = e->wide_val ? 8u : value_ids(!e->compact && !e->wide);
     e->cons_bytes = cons_bytes_per_item(spec, e->wide, e->lpi, e->msize, c.key_window, c.variants, e->nval);
     // key-lifetime kernel (brc_life.h): NPAD = 64 consensus under a two-class delay model with D <= 8
     // or per-link (uniform / geometric) delays with D <= 8, proposals from Philox or loaded, no event
@@ -637,7 +651,9 @@ int brc_load_proposals(void* h, const int8_t* proposals) {
     bool wide_ids = false;
     for (size_t i = 0; i < bytes; ++i) {
         if (proposals[i] < 0 || proposals[i] > vmax) {
-            e->err = "proposal value ids must be in [0, " + std::to_string(vmax) + "] on this kernel";
+            e->err = "proposal value ids must be in [0, " + std::to_string(vmax) + "] on this kernel" +
+                     ((e->wide && !e->wide_val && e->cfg.mode != BRC_MODE_SPEC && e->cfg.peer_mode == BRC_PEER_SENDER)
+                          ? " (ids 4..7 at n > 64: create the engine with BRC_FLAG_WIDE_VALUES)" : "");
             return BRC_E_INVALID;
         }
         wide_ids = wide_ids || proposals[i] > 3;
@@ -694,7 +710,8 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
         const brc_injection& x = list[i];
         if (x.instance >= c.instances || x.node >= c.n || x.t > c.step_cap) { e->err = "injection out of range"; return BRC_E_INVALID; }
         if (x.value < 0 || x.value >= (int)(c.mode == BRC_MODE_SPEC ? 4u : e->nval) || x.s >= 0xFFFE) {
-            e->err = "value id / phase index out of range (value ids 4..7 need n <= 32 or connection peers, not SPEC)";
+            e->err = "value id / phase index out of range (value ids 4..7 need n <= 32, connection peers up to n = 64, "
+                     "BRC_FLAG_GENERAL_KEYS at n in 33..64 or BRC_FLAG_WIDE_VALUES at n > 64 with sender peers; not SPEC)";
             return BRC_E_INVALID;
         }
         bool drop = false;                       // a repeated SEND carried on no link (sender peers)
@@ -1068,7 +1085,7 @@ int brc_run(void* h, uint32_t max_steps, uint32_t* running_left) {
         e->life_done = true;
     } else {
         rc = e->regmask ? launch_step_64r(e->dm, c.event_capacity != 0, kmode, blocks, e->lds_bytes, e->stream, e->dparams)
-                        : launch_step(e->npad, e->dm, c.event_capacity != 0, kmode, e->wide_wv4, e->wide_rec, blocks,
+                        : launch_step(e->npad, e->dm, c.event_capacity != 0, kmode, e->wide_wv4, e->wide_rec, e->wide_val, blocks,
                                       e->lds_bytes, e->stream, e->dparams);
     }
     if (rc == BRC_E_INVALID) { e->err = "no kernel instantiation"; return rc; }

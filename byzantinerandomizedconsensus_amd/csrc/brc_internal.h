@@ -169,7 +169,8 @@ constexpr uint32_t WREC_NODE_SH = 56;
 
 // Consensus value ids (core/byzantinerandomizedconsensus.py:57-60 keys its tables by payload string;
 // id 0 is str(NONE) == "-1"): 2 bits (3 strings + "-1") on the lean, wide and key-lifetime kernels,
-// 3 bits (7 strings + "-1") on the other narrow kernels (NPAD <= 32, and connection peers).
+// 3 bits (7 strings + "-1") on the other narrow kernels (NPAD <= 32, and connection peers) and on the wide
+// kernels of an engine created with BRC_FLAG_WIDE_VALUES (brc_step_wide.h V8: brc_create sets nval itself).
 __host__ __device__ constexpr uint32_t value_ids(bool narrow_full) { return narrow_full ? 8u : 4u; }
 
 // Consensus record word 0 (cons0): round [0,16) | phase [16,20) | nvals [20,24) | order [24,48) (the
@@ -229,6 +230,7 @@ __host__ __device__ inline uint32_t lds_bytes_per_wave(int npad, uint32_t NK, ui
 // xb[2][CHUNK_W][nL][2][NW] u64 | outm[16][NW] u64 | sq[Q][NPAD] u8 | fresh[nkw] u64 | klist[NK] u16 |
 // red[12] u32 | pmw[2][CHUNK_W][NW] u32
 // consensus area: REFERENCE hm[4][NW][NPAD] u64;  SPEC cnt[Q][NPAD] u32 (one key variant per origin)
+// (3-bit value ids, BRC_FLAG_WIDE_VALUES: the same carve -- host-mask planes 4..7 stay in the HBM buffer)
 __host__ __device__ inline uint32_t cons_words_wide(bool spec, uint32_t npad, uint32_t Q) {
     const uint32_t nw = npad / 64;
     return spec ? (Q * npad + 1) / 2 : 4 * nw * npad;
@@ -305,5 +307,8 @@ int launch_step_256(int dm, bool events, int mode, bool wv4, uint32_t blocks, ui
 // ... with restricted ECHO / READY records (BRC_FLAG_WIDE_RECORDS; brc_kern_128x.hip / brc_kern_256x.hip)
 int launch_step_128x(int dm, bool events, int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
 int launch_step_256x(int dm, bool events, int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
+// ... with 3-bit consensus value ids as well (BRC_FLAG_WIDE_VALUES; brc_kern_128v.hip / brc_kern_256v.hip)
+int launch_step_128v(int dm, bool events, int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
+int launch_step_256v(int dm, bool events, int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
 
 }  // namespace brc

@@ -67,12 +67,20 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t x) {
 // in use) and each receiver lane adds its own hits to the ballot-derived counts.  An extra SEND of a key (a payload
 // SENT by a second node, or again) is a record of the same table with message type 0: the slot keeps the first SEND,
 // and a cell's SEND arrivals of one step become a count.  false: none of this is compiled.
-template <int NPAD, int DM, bool EV, int MODE, int WV = 0, bool REC = false>
+// V8 (BRC_FLAG_WIDE_VALUES): 3-bit consensus value ids (seven proposal strings besides "-1").  `order` packs 3-bit
+// fields and a replica keeps eight host masks: planes 0..3 in LDS as without it, planes 4..7 in place in the HBM
+// buffer (P.hmask, [instance][8][NW][NPAD]) -- eight LDS planes are 64 KB at NPAD 256, one workgroup per CU where
+// three fit now, while a plane above 3 is touched only by a delivery that carries such an id.  Each lane reads and
+// writes its own column only.  Such engines run the REC form (brc_create).  false: 2-bit ids, four planes.
+template <int NPAD, int DM, bool EV, int MODE, int WV = 0, bool REC = false, bool V8 = false>
 __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ? BRC_WIDE_WAVES16 : BRC_WIDE_WAVES)) void brc_step_wide(const Params* __restrict__ pp) {
     const Params& P = *pp;
     constexpr bool SPEC = MODE == BRC_MODE_SPEC, BEB = MODE == BRC_MODE_BEB, CONN = MODE == KMODE_CONN;
     // u64 words per cell: CONN adds the lane's ECHO and READY send-count rings (Ring16, brc_step.h)
     constexpr uint32_t CW = CONN ? 5 : 1;
+    // consensus value ids: VB bits each, NVAL of them; VREP has a 1 in the low bit of every VB-bit field of `order`
+    constexpr uint32_t NVAL = V8 ? 8u : 4u, VB = V8 ? 3u : 2u, VMASK = NVAL - 1u, VREP = V8 ? 0x249249u : 0x55u;
+    static_assert(!V8 || (REC && !SPEC && !CONN && WV == 0), "3-bit value ids: the record form, reference / best-effort");
     // DM > 8 (geometric): in a given wave most delays carry no send, so each wave publishes which
     // did (pmw) and the readers visit only those; with DM <= 8 that bookkeeping costs more than it
     // saves (measured cfg5: geometric -20% kernel time, const/uniform +5%)
@@ -101,7 +109,7 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
     // dpos: this pass's deliveries, one bit per key-list POSITION (not per key slot): a step's keys
     // are processed in passes of at most 64 DCW keys, which bounds the delivery bitmap (a slot-
     // indexed one would take NK x NPAD bits and cap the CU at one workgroup)
-    // consensus area: REFERENCE hm[4][NW][NPAD] u64;  SPEC cnt[Q][NPAD] u32
+    // consensus area: REFERENCE hm[4][NW][NPAD] u64 (V8: planes 4..7 stay in HBM);  SPEC cnt[Q][NPAD] u32
     uint64_t* s_meta = smem;
     uint64_t* s_act = s_meta + NK;
     const uint32_t DCW = dpos_words_wide(nkw);     // delivery-bitmap words per receiver
@@ -130,7 +138,7 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
     ItemState its = P.items[inst];
     uint32_t t = its.t, inj_pos = its.inj_pos;
     const uint32_t inj_off = gp(P.inj_off)[inst], inj_cnt = gp(P.inj_cnt)[inst];
-    for (uint32_t i = d; i < NK; i += NPAD)   // restricted-SEND flag in bit 63 of the LDS copy (value ids < 4)
+    for (uint32_t i = d; i < NK; i += NPAD)   // restricted-SEND flag in bit 63 of the LDS copy (value ids < 8)
         s_meta[i] = gp(P.meta)[inst * NK + i] | ((gp(P.mgen)[inst * NK + i] & GEN_RESTRICTED) ? M_RESTRICTED : 0ull);
     if (d < nkw) s_fresh[d] = 0;
     for (uint32_t i = d; i < TS * nkw; i += NPAD) s_act[i] = gp(P.act)[inst * TS * nkw + i];
@@ -275,12 +283,16 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
     auto hm = [&](uint32_t v, uint32_t w) -> uint64_t& { return s_hm[(v * NW + w) * NPAD + d]; };
     auto cnt = [&](uint32_t q) -> uint32_t& { return s_cnt[q * NPAD + d]; };
     const gptr_t<uint32_t> gcnt = gp((uint32_t*)P.hmask);
+    // V8: this lane's word w of plane v in the HBM buffer (planes 4..7 are read and written there)
+    auto ghm = [&](uint32_t v, uint32_t w) -> gptr_t<uint64_t> {
+        return gp((uint64_t*)P.hmask) + ((inst * NVAL + v) * NW + w) * NPAD + d;
+    };
     if constexpr (SPEC) {
         for (uint32_t q = 0; q < Q; ++q) cnt(q) = cons_lane ? gcnt[(inst * Q + q) * NPAD + d] : 0u;
     } else {
         for (uint32_t v = 0; v < 4; ++v)
             for (uint32_t w = 0; w < NW; ++w)
-                hm(v, w) = cons_lane ? gp((const uint64_t*)P.hmask)[((inst * 4 + v) * NW + w) * NPAD + d] : 0ull;
+                hm(v, w) = cons_lane ? gp((const uint64_t*)P.hmask)[((inst * NVAL + v) * NW + w) * NPAD + d] : 0ull;
     }
     uint32_t round = c0 & 0xFFFF, phase = (c0 >> 16) & 0xF, nvals = (c0 >> 20) & 0xF;   // cons0_pack
     uint32_t order = (c0 >> 24) & 0xFFFFFF, vcount = (c0 >> 48) & 0xFFFF;
@@ -379,28 +391,49 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
     };
     auto popc_hm = [&](uint32_t v) -> uint32_t {
         uint32_t c = 0;
+        if constexpr (V8) {
+            if (v >= 4) {
+                for (uint32_t w = 0; w < NW; ++w) c += (uint32_t)__popcll(*ghm(v, w));
+                return c;
+            }
+        }
         for (uint32_t w = 0; w < NW; ++w) c += (uint32_t)__popcll(hm(v, w));
         return c;
     };
     auto get_max_val = [&](uint32_t bound2) -> uint32_t {          // :64-68
         for (uint32_t i = 0; i < nvals; ++i) {
-            const uint32_t v = (order >> (2 * i)) & 3;
+            const uint32_t v = (order >> (VB * i)) & VMASK;
             if (2 * popc_hm(v) > bound2) return v;
         }
         return 0;                                                    // str(NONE) == "-1"
     };
     auto cons_reset = [&]() {
+        if constexpr (V8) {
+            // the HBM planes in use are the ids above 3 in `order` (a plane is non-zero only after an insertion)
+            for (uint32_t i = 0; i < nvals; ++i) {
+                const uint32_t v = (order >> (VB * i)) & VMASK;
+                if (v >= 4)
+                    for (uint32_t w = 0; w < NW; ++w) *ghm(v, w) = 0;
+            }
+        }
         vcount = 0; nvals = 0; order = 0;
         for (uint32_t v = 0; v < 4; ++v)
             for (uint32_t w = 0; w < NW; ++w) hm(v, w) = 0;
     };
     // :53-106 for a message of `host` carrying value id v (a BRB delivery, or BRC_INJ_DELIVER)
     auto cons_deliver_vh = [&](uint32_t v, uint32_t host, bool defer) {
-        // v already inserted? every 2-bit field of `order` compared at once (nvals <= 4)
-        const uint32_t x = order ^ (v * 0x55u);
-        const bool found = (~(x | (x >> 1)) & 0x55u & ((1u << (2 * nvals)) - 1u)) != 0;
-        if (!found) { order |= v << (2 * nvals); ++nvals; }         // :57-58
-        hm(v, host >> 6) |= 1ull << (host & 63);                     // :60
+        // v already inserted? every VB-bit field of `order` compared at once (nvals <= NVAL)
+        const uint32_t x = order ^ (v * VREP);
+        bool found;
+        if constexpr (V8) found = (~(x | (x >> 1) | (x >> 2)) & VREP & ((1u << (VB * nvals)) - 1u)) != 0;
+        else found = (~(x | (x >> 1)) & VREP & ((1u << (VB * nvals)) - 1u)) != 0;
+        if (!found) { order |= v << (VB * nvals); ++nvals; }        // :57-58
+        if constexpr (V8) {
+            if (v >= 4) *ghm(v, host >> 6) |= 1ull << (host & 63);
+            else hm(v, host >> 6) |= 1ull << (host & 63);
+        } else {
+            hm(v, host >> 6) |= 1ull << (host & 63);                 // :60
+        }
         ++vcount;                                                    // :61
         if (vcount >= P.T_cnt && phase == 1) {                       // :71
             const uint32_t prop = get_max_val(P.bound_p1);           // :73
@@ -417,7 +450,7 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
             if (defer) send_later(2 * (round - 1), dec); else send_key(2 * (round - 1), dec);   // :102-106
         }
     };
-    auto cons_deliver = [&](uint32_t k) { cons_deliver_vh(m_value(s_meta[k]) & 3, k >> ksh, true); };
+    auto cons_deliver = [&](uint32_t k) { cons_deliver_vh(m_value(s_meta[k]) & VMASK, k >> ksh, true); };
 
     // ---- SPEC consensus (as brc_step.h spec_advance / spec_deliver)
     auto spec_advance = [&](bool defer) {
@@ -468,7 +501,7 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
                 const uint32_t v = (P.proposals == BRC_PROPOSALS_PHILOX) ? proposal_id(P.seed, g, d)
                                                                          : (uint32_t)gp(P.prop)[inst * n + d];
                 round = 1; phase = 1;                                 // :43-47
-                send_key(0, v & 3);
+                send_key(0, v & VMASK);
                 if constexpr (SPEC) spec_advance(false);              // phase 0 may be buffered
             }
             clear_fresh();
@@ -481,13 +514,13 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
             mine_any |= mine;
             if (r.kind == BRC_INJ_PROPOSE) {
                 if (mine && honest && d == r.node) {
-                    round = 1; phase = 1; send_key(0, (uint32_t)r.value & 3);
+                    round = 1; phase = 1; send_key(0, (uint32_t)r.value & VMASK);
                     if constexpr (SPEC) spec_advance(false);
                 }
             } else if (r.kind == BRC_INJ_DELIVER) {
                 // a direct deliver() call (brc_inject refuses it for SPEC): host in r.slot
                 if constexpr (!SPEC) {
-                    if (mine && honest && d == r.node) cons_deliver_vh((uint32_t)r.value & 3, r.slot, false);
+                    if (mine && honest && d == r.node) cons_deliver_vh((uint32_t)r.value & VMASK, r.slot, false);
                 }
             } else if (r.kind == BRC_INJ_SEND || r.kind == BRC_INJ_KEY) {
                 const bool is_send = r.kind == BRC_INJ_SEND;
@@ -1092,7 +1125,7 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
             for (uint32_t q = 0; q < Q; ++q) gcnt[(inst * Q + q) * NPAD + d] = cnt(q);
         } else {
             for (uint32_t v = 0; v < 4; ++v)
-                for (uint32_t w = 0; w < NW; ++w) gp((uint64_t*)P.hmask)[((inst * 4 + v) * NW + w) * NPAD + d] = hm(v, w);
+                for (uint32_t w = 0; w < NW; ++w) gp((uint64_t*)P.hmask)[((inst * NVAL + v) * NW + w) * NPAD + d] = hm(v, w);
         }
     }
     // statistics: wave sums, then one atomic per wave and counter
@@ -1120,9 +1153,9 @@ __global__ __launch_bounds__(NPAD, (EV ? BRC_MIN_WAVES_EV : WV ? WV : DM == 16 ?
     }
 }
 
-template <int NPAD, int DMX, bool EV, int MODE, int WV = 0, bool REC = false>
+template <int NPAD, int DMX, bool EV, int MODE, int WV = 0, bool REC = false, bool V8 = false>
 int launch_wide_one(uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P) {
-    auto kern = brc_step_wide<NPAD, DMX, EV, MODE, WV, REC>;
+    auto kern = brc_step_wide<NPAD, DMX, EV, MODE, WV, REC, V8>;
     if (lds > 64 * 1024 &&
         hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return BRC_E_HIP;
@@ -1164,6 +1197,21 @@ int launch_step_wide_rec(int dm, bool events, int mode, uint32_t blocks, uint32_
         if (mode == BRC_MODE_SPEC) return events ? launch_wide_one<NPAD, DMX, true, BRC_MODE_SPEC, 0, true>(blocks, lds, s, P) : launch_wide_one<NPAD, DMX, false, BRC_MODE_SPEC, 0, true>(blocks, lds, s, P); \
         if (mode == BRC_MODE_BEB) return events ? launch_wide_one<NPAD, DMX, true, BRC_MODE_BEB, 0, true>(blocks, lds, s, P) : launch_wide_one<NPAD, DMX, false, BRC_MODE_BEB, 0, true>(blocks, lds, s, P); \
         if (mode == BRC_MODE_REFERENCE) return events ? launch_wide_one<NPAD, DMX, true, BRC_MODE_REFERENCE, 0, true>(blocks, lds, s, P) : launch_wide_one<NPAD, DMX, false, BRC_MODE_REFERENCE, 0, true>(blocks, lds, s, P); \
+        return BRC_E_INVALID;                                                                          \
+    }
+    BRC_CASE(4) BRC_CASE(8) BRC_CASE(16)
+#undef BRC_CASE
+    return BRC_E_INVALID;
+}
+
+// the V8 instantiations (BRC_FLAG_WIDE_VALUES: 3-bit value ids; always the record form, reference and best-effort
+// protocols), in units of their own (brc_kern_<NPAD>v.hip)
+template <int NPAD>
+int launch_step_wide_v8(int dm, bool events, int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P) {
+#define BRC_CASE(DMX)                                                                                  \
+    if (dm == DMX) {                                                                                   \
+        if (mode == BRC_MODE_BEB) return events ? launch_wide_one<NPAD, DMX, true, BRC_MODE_BEB, 0, true, true>(blocks, lds, s, P) : launch_wide_one<NPAD, DMX, false, BRC_MODE_BEB, 0, true, true>(blocks, lds, s, P); \
+        if (mode == BRC_MODE_REFERENCE) return events ? launch_wide_one<NPAD, DMX, true, BRC_MODE_REFERENCE, 0, true, true>(blocks, lds, s, P) : launch_wide_one<NPAD, DMX, false, BRC_MODE_REFERENCE, 0, true, true>(blocks, lds, s, P); \
         return BRC_E_INVALID;                                                                          \
     }
     BRC_CASE(4) BRC_CASE(8) BRC_CASE(16)

@@ -22,7 +22,9 @@ Deviations from the reference, all reported by exceptions and never silent:
   ``core/byzantinerandomizedconsensus.py:102-106``).  Clusters stop once every node has
   decided ``round_cap`` times (``configure``).
 * At most seven distinct proposal strings besides ``"-1"`` (three-bit value ids) -- three on
-  clusters above 64 nodes (and best-effort broadcast above 32), whose kernels keep two-bit ids.
+  clusters above 64 nodes with connection peers (and best-effort broadcast above 32), whose
+  kernels keep two-bit ids.  A consensus cluster above 64 nodes with sender peers runs the wide
+  kernels' three-bit form (brc.h BRC_FLAG_WIDE_VALUES).
 * A payload SENT by two different origins (or SENT again) is one key in the reference (its
   dicts are keyed by the payload string); the engine models it as one key with extra SENDs
   (brc_step.h extra-SEND records: up to 16 per wave item, shared by the instances packed into
@@ -165,10 +167,10 @@ class Cluster:
         self.sent = set()          # keys SENT (a payload may be declared first by an ECHO / READY)
         # three-bit value ids on the narrow kernels that keep them (include/brc.h brc_injection.value)
         n = len(peers)
-        # the wide kernel (> 64 nodes): two-bit value ids, and one SEND per key unless the engine keeps records
-        # (one_send).  33..64 nodes with sender peers run the narrow kernel's general form
-        # (BRC_FLAG_GENERAL_KEYS), which keeps what n <= 32 keeps
-        self.two_bit_ids = n > 64
+        # the wide kernel (> 64 nodes): two-bit value ids with connection peers (three-bit ones with sender peers:
+        # wide_values), and one SEND per key unless the engine keeps records (one_send).  33..64 nodes with sender
+        # peers run the narrow kernel's general form (BRC_FLAG_GENERAL_KEYS), which keeps what n <= 32 keeps
+        self.two_bit_ids = n > 64 and cfg["peer_mode"] != "sender"
         self.values = ValueTable(4 if self.two_bit_ids else 8)
         self.engine = None
         self.seen_events = 0
@@ -225,6 +227,12 @@ class Cluster:
         """A broadcast cluster above 64 nodes with sender peers: its engine keeps extra SENDs of a key as
         records (brc.h BRC_FLAG_WIDE_RECORDS; brc_create refuses the flag with connection peers)."""
         return len(self.peers) > 64 and not self.beb and not self.cons and self.cfg["peer_mode"] == "sender"
+
+    @property
+    def wide_values(self):
+        """A consensus cluster above 64 nodes with sender peers: its engine keeps three-bit value ids (brc.h
+        BRC_FLAG_WIDE_VALUES; brc_create refuses the flag with connection peers)."""
+        return len(self.peers) > 64 and not self.beb and bool(self.cons) and self.cfg["peer_mode"] == "sender"
 
     @property
     def one_send(self):
@@ -312,7 +320,8 @@ class Cluster:
                              event_capacity=c["event_capacity"], instance_offset=c["instance_id"],
                              device=c["device"], mode=L.MODE_BEB if self.beb else L.MODE_REFERENCE,
                              peer_mode=L.PEER_SENDER if self.beb else PEER_MODES[c["peer_mode"]],
-                             general_keys=not self.beb, wide_records=self.wide_records)
+                             general_keys=not self.beb, wide_records=self.wide_records,
+                             wide_values=self.wide_values)
 
     def _flush(self):
         if self.actions:

@@ -24,6 +24,8 @@ Workloads:
   cfg5-*     n=256 f=85 SPEC, 6144 instances per GPU, const / uniform[1,4] / geometric<=16
   cfg5-conn-uniform  n=256 f=85, connection-identity peers (the reference as shipped), reference
              protocol, uniform[1,4] delays, 6144 instances per GPU (the wide kernel's 40-B cells)
+  cfg5-ref-slow[-wval]  n=256 f=85, reference protocol, slow-set D=8, round cap 1, 6144 instances per GPU;
+             -wval: the same under BRC_FLAG_WIDE_VALUES (three-bit value ids), binary proposals
 
 A step is one pass of the hot path over the batch (reset + run to completion); the timed region
 is K steps between barriers, max over ranks.  `roofline.achieved` = this layout's algorithmic
@@ -111,6 +113,12 @@ def workloads(L):
         # the same with BRC_FLAG_WIDE_RECORDS and an empty record table: what opting in to restricted ECHO / READY
         # records costs a run that injects none (no 4-waves-per-SIMD instantiation, one more word tested per step)
         W["cfg5-" + name + "-rec"] = (6144, True, dict(W["cfg5-" + name][2], wide_records=True))
+    # cfg5's committee under the reference protocol (slow-set D = 8, round cap 1), and the same with
+    # BRC_FLAG_WIDE_VALUES and the same binary proposals: what opting in to three-bit value ids costs a run that
+    # proposes two strings (the record form's kernels, 3-bit `order` fields, host-mask planes 4..7 left in HBM untouched)
+    W["cfg5-ref-slow"] = (6144, True, dict(base, n=256, f=85, seed=0x5EED0005, delay_model=slow, delay_max=8,
+                                           round_cap=1, key_window=8))
+    W["cfg5-ref-slow-wval"] = (6144, True, dict(W["cfg5-ref-slow"][2], wide_values=True))
     return W
 
 

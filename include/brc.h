@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define BRC_ABI_VERSION 8
+#define BRC_ABI_VERSION 9
 
 enum {
     BRC_OK = 0,
@@ -118,8 +118,16 @@ typedef struct {
  * instantiations that take records: restricted ECHO / READY (below) and extra SENDs of one key (brc_injection.dst_mask).
  * Opt-in: an engine without the flag launches the kernels it always did and refuses such records; with it the 4-waves-per-SIMD instantiations are not used and
  * every step tests one more word, so a run without records is slightly slower.  With n <= 64 or
- * connection peers brc_create fails with BRC_E_INVALID and a reason. */
-enum { BRC_FLAG_GENERAL_KEYS = 1, BRC_FLAG_WIDE_RECORDS = 2 };
+ * connection peers brc_create fails with BRC_E_INVALID and a reason.
+ * BRC_FLAG_WIDE_VALUES (v9): at n > 64 with sender peers, BRC_MODE_REFERENCE or BRC_MODE_BEB (either protocol), run
+ * the wide kernel's instantiations that keep 3-bit value ids: value 0..7 in brc_injection (SEND, KEY,
+ * BRC_INJ_DELIVER) and in brc_load_proposals, seven proposal strings besides "-1" as on the narrow kernels.  They are
+ * the record form as well: such an engine accepts everything a BRC_FLAG_WIDE_RECORDS engine accepts, and the two
+ * flags together select the same kernels.  Opt-in: an engine without the flag launches the kernels it always did
+ * and refuses ids >= 4.  A replica's host masks of ids 4..7 stay in device memory rather than LDS, so binary
+ * workloads cost what BRC_FLAG_WIDE_RECORDS costs and a delivery of such an id a few global accesses.
+ * With n <= 64, connection peers or BRC_MODE_SPEC brc_create fails with BRC_E_INVALID and a reason. */
+enum { BRC_FLAG_GENERAL_KEYS = 1, BRC_FLAG_WIDE_RECORDS = 2, BRC_FLAG_WIDE_VALUES = 4 };
 
 /* Injections may arrive between brc_run calls.  A record's time must not lie before the step its instance's wave
  * item stands at (brc_instance_result.t_now once the engine has run): t < t_now is BRC_E_STATE.  t == t_now is
@@ -158,15 +166,17 @@ typedef struct {
     uint32_t kp;              /* key slot: origin * variants + variant */
     uint32_t s;               /* phase index 2*(round-1)+(phase-1), or BRB sequence */
     int32_t value;            /* value id (0 == "-1"): 0..7 on the narrow kernels that keep 3-bit ids
-                                 (n <= 32, or connection peers at n <= 64; not BRC_MODE_SPEC), 0..3 on
-                                 the others (n in 33..64 with sender peers, n > 64, SPEC); larger:
-                                 BRC_E_INVALID.  The same range holds for brc_load_proposals */
+                                 (n <= 32, or connection peers at n <= 64; not BRC_MODE_SPEC) and on the
+                                 wide kernels of an engine created with BRC_FLAG_WIDE_VALUES (n > 64,
+                                 sender peers, not SPEC), 0..3 on the others (n in 33..64 with sender
+                                 peers, n > 64 without the flag, SPEC); larger: BRC_E_INVALID.  The
+                                 same range holds for brc_load_proposals */
     uint64_t dst_mask;        /* BRC_INJ_SEND / BRC_INJ_MSG destinations 0..63.  A second
                                  SEND of a key (another node, or the same again: one payload string
                                  SENT twice, one key in the reference) is an extra SEND on the
                                  narrow kernels that keep 3-bit value ids and, at n > 64 with sender
                                  peers, on an engine created with BRC_FLAG_WIDE_RECORDS (value ids
-                                 stay 2 bits there).  It must not precede the key's first SEND
+                                 stay 2 bits there) or BRC_FLAG_WIDE_VALUES.  It must not precede the key's first SEND
                                  (BRC_BADINJ for its instance), travels on the links of its
                                  destination set that its node has not used for a SEND of the key
                                  (sender peers; with none left it is accepted and changes nothing)
@@ -253,7 +263,8 @@ int brc_read_round_histogram(void* engine, uint64_t* hist, uint32_t bins);
  * (the agreement check of SURVEY §8(e)).  Per engine; shard.reduce_stats all-reduces them. */
 int brc_read_decisions(void* engine, uint64_t* value_hist /* [5] */, uint64_t* disagreements);
 /* The same over 3-bit value ids: value_hist[v] for v = 0..7, value_hist[8] never decided.
- * brc_read_decisions is BRC_E_STATE once a value id >= 4 was decided. */
+ * brc_read_decisions is BRC_E_STATE once a value id >= 4 was decided, on a narrow kernel or on an
+ * engine created with BRC_FLAG_WIDE_VALUES alike: this call serves those. */
 int brc_read_value_decisions(void* engine, uint64_t* value_hist /* [9] */, uint64_t* disagreements);
 /* brc_reset, then re-key the engine to the global instances [instance_offset, +instances): one
  * engine sweeps a range larger than its device footprint in tiles, with the results one engine
