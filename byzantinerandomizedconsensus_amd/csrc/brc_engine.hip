@@ -450,11 +450,14 @@ int brc_create(const brc_config* cfg, void** out) {
         // more than 8 live phase indices per origin: reference / best-effort protocols on the narrow kernels
         // (up to 128: the reference protocol's many-round runs; the lean kernels take <= 32 and
         // leave larger windows to the key-lifetime kernel, below)
-        c.key_window * c.variants > ((c.mode != BRC_MODE_SPEC && c.n <= 64) ? 128u : 8u) ||
+        // ... and 16 or 32 on the wide kernels of an engine created with BRC_FLAG_WIDE_WINDOWS (validated below)
+        c.key_window * c.variants > ((c.mode != BRC_MODE_SPEC && c.n <= 64) ? 128u
+                                     : (c.flags & BRC_FLAG_WIDE_WINDOWS)    ? 32u : 8u) ||
         c.f >= c.n || (c.byz_pattern == BRC_BYZ_EQUIVOCATE && c.variants < 2) ||
         (c.byz_pattern != BRC_BYZ_NONE && c.byz_pattern != BRC_BYZ_EQUIVOCATE) ||
         c.proposals > BRC_PROPOSALS_LOADED || c.mode > BRC_MODE_BEB ||
-        (c.flags & ~(uint32_t)(BRC_FLAG_GENERAL_KEYS | BRC_FLAG_WIDE_RECORDS | BRC_FLAG_WIDE_VALUES)) ||
+        (c.flags & ~(uint32_t)(BRC_FLAG_GENERAL_KEYS | BRC_FLAG_WIDE_RECORDS | BRC_FLAG_WIDE_VALUES |
+                               BRC_FLAG_WIDE_WINDOWS)) ||
         // the general form at NPAD = 64 with sender peers is the reference protocol's (KMODE_XREF)
         ((c.flags & BRC_FLAG_GENERAL_KEYS) && c.n > 32 && c.n <= 64 && c.peer_mode == BRC_PEER_SENDER &&
          c.mode != BRC_MODE_REFERENCE) ||
@@ -478,6 +481,14 @@ int brc_create(const brc_config* cfg, void** out) {
                                                  "keep 2-bit value ids";
         return BRC_E_INVALID;
     }
+    if ((c.flags & BRC_FLAG_WIDE_WINDOWS) && (c.n <= 64 || c.peer_mode != BRC_PEER_SENDER || c.mode == BRC_MODE_SPEC)) {
+        g_create_err = c.n <= 64 ? "BRC_FLAG_WIDE_WINDOWS is for the wide kernels (n > 64): the narrow kernels take key windows "
+                                   "up to 128 without it"
+                     : c.mode == BRC_MODE_SPEC ? "BRC_FLAG_WIDE_WINDOWS: not with BRC_MODE_SPEC, whose per-phase windows stay <= 8"
+                                               : "BRC_FLAG_WIDE_WINDOWS needs sender peers: the connection-peer wide kernels "
+                                                 "(five words per cell) keep key_window * variants <= 8";
+        return BRC_E_INVALID;
+    }
     Engine* e = new Engine();
     e->cfg = c;
     e->npad = pick_npad(c.n);
@@ -488,6 +499,8 @@ int brc_create(const brc_config* cfg, void** out) {
     e->lpi = e->wide ? (uint32_t)e->npad : 64u;
     e->bw = e->wide ? (uint32_t)e->npad / 64 : 1u;
     e->nkw_t = e->npad / 8 < 1 ? 1 : e->npad / 8;
+    // BRC_FLAG_WIDE_WINDOWS: up to 32 key slots per replica lane (NK <= 32 NPAD), as far as the LDS carve allows
+    if (e->npad > 64 && (c.flags & BRC_FLAG_WIDE_WINDOWS)) e->nkw_t = e->npad / 2;
     e->NK = (uint32_t)e->npad * c.variants * c.key_window;
     // narrow kernel: + the trash row (brc_step.h); connection peers: 5 words per cell (the cell word
     // and two 16-step send-count rings, brc_step.h Ring16)

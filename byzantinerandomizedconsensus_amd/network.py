@@ -235,6 +235,19 @@ class Cluster:
         return len(self.peers) > 64 and not self.beb and bool(self.cons) and self.cfg["peer_mode"] == "sender"
 
     @property
+    def wide_windows(self):
+        """A consensus cluster above 64 nodes with sender peers: its engine keeps 16 phase indices per origin in flight
+        (brc.h BRC_FLAG_WIDE_WINDOWS; brc_create refuses the flag with connection peers) -- the reference protocol's
+        phase leakage needs more than 8 from about its fourth round on.  16 fits every delay model; 32 would not at
+        more than 128 nodes under per-link delays above 8."""
+        return len(self.peers) > 64 and not self.beb and bool(self.cons) and self.cfg["peer_mode"] == "sender"
+
+    @property
+    def key_window(self):
+        """Phase indices per origin the cluster's engine keeps in flight (brc_config.key_window)."""
+        return 16 if self.wide_windows else 8
+
+    @property
     def one_send(self):
         """The cluster's kernel models one SEND per key: the lean kernels (best-effort broadcast above 32
         nodes) and the wide kernels without records."""
@@ -316,12 +329,12 @@ class Cluster:
                              delay_model=c["delay_model"], delay_max=c["delay_max"],
                              delay_const=c["delay_const"],
                              round_cap=c["round_cap"] if self.cons else 0, step_cap=c["step_cap"],
-                             key_window=8, variants=1, byzantine=silent,
+                             key_window=self.key_window, variants=1, byzantine=silent,
                              event_capacity=c["event_capacity"], instance_offset=c["instance_id"],
                              device=c["device"], mode=L.MODE_BEB if self.beb else L.MODE_REFERENCE,
                              peer_mode=L.PEER_SENDER if self.beb else PEER_MODES[c["peer_mode"]],
                              general_keys=not self.beb, wide_records=self.wide_records,
-                             wide_values=self.wide_values)
+                             wide_values=self.wide_values, wide_windows=self.wide_windows)
 
     def _flush(self):
         if self.actions:

@@ -26,6 +26,8 @@ Workloads:
              protocol, uniform[1,4] delays, 6144 instances per GPU (the wide kernel's 40-B cells)
   cfg5-ref-slow[-wval]  n=256 f=85, reference protocol, slow-set D=8, round cap 1, 6144 instances per GPU;
              -wval: the same under BRC_FLAG_WIDE_VALUES (three-bit value ids), binary proposals
+  cfg5-ref-slow-q16  the same committee to round cap 6 through a key window of 16 (BRC_FLAG_WIDE_WINDOWS), 384
+             instances per GPU (informational: no earlier build runs it)
 
 A step is one pass of the hot path over the batch (reset + run to completion); the timed region
 is K steps between barriers, max over ranks.  `roofline.achieved` = this layout's algorithmic
@@ -119,6 +121,9 @@ def workloads(L):
     W["cfg5-ref-slow"] = (6144, True, dict(base, n=256, f=85, seed=0x5EED0005, delay_model=slow, delay_max=8,
                                            round_cap=1, key_window=8))
     W["cfg5-ref-slow-wval"] = (6144, True, dict(W["cfg5-ref-slow"][2], wide_values=True))
+    # ... to round cap 6 through a key window of 16 (BRC_FLAG_WIDE_WINDOWS; 8 MB of cells per instance): without the
+    # flag brc_create refuses the window, and at window 8 the run stops with BRC_OVERFLOW around its fourth round
+    W["cfg5-ref-slow-q16"] = (384, True, dict(W["cfg5-ref-slow"][2], round_cap=6, key_window=16, wide_windows=True))
     return W
 
 

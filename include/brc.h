@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define BRC_ABI_VERSION 9
+#define BRC_ABI_VERSION 10
 
 enum {
     BRC_OK = 0,
@@ -95,8 +95,9 @@ typedef struct {
                                  phases of one origin in flight by round 8 and 127 by round 64 under
                                  slow-set D = 8; above 32 at n in 33..64 with sender peers, and
                                  Q * NV = 128 at n in 33..64 with connection peers: the key-lifetime
-                                 kernel only) */
-    uint32_t variants;        /* NV: key variants per origin (1, 2 or 4; Q*NV <= 8, <= 128 where Q may be) */
+                                 kernel only; 16 and 32 at n > 64 with BRC_FLAG_WIDE_WINDOWS, below) */
+    uint32_t variants;        /* NV: key variants per origin (1, 2 or 4; Q*NV <= 8, <= 128 where Q may be,
+                                 <= 32 at n > 64 with BRC_FLAG_WIDE_WINDOWS) */
     uint32_t proposals;       /* BRC_PROPOSALS_* (consensus) */
     uint32_t byz_pattern;     /* BRC_BYZ_* applied to every instance */
     uint32_t event_capacity;  /* 0: no event log */
@@ -126,8 +127,24 @@ typedef struct {
  * flags together select the same kernels.  Opt-in: an engine without the flag launches the kernels it always did
  * and refuses ids >= 4.  A replica's host masks of ids 4..7 stay in device memory rather than LDS, so binary
  * workloads cost what BRC_FLAG_WIDE_RECORDS costs and a delivery of such an id a few global accesses.
- * With n <= 64, connection peers or BRC_MODE_SPEC brc_create fails with BRC_E_INVALID and a reason. */
-enum { BRC_FLAG_GENERAL_KEYS = 1, BRC_FLAG_WIDE_RECORDS = 2, BRC_FLAG_WIDE_VALUES = 4 };
+ * With n <= 64, connection peers or BRC_MODE_SPEC brc_create fails with BRC_E_INVALID and a reason.
+ * BRC_FLAG_WIDE_WINDOWS (v10): at n > 64 with sender peers, BRC_MODE_REFERENCE or BRC_MODE_BEB (either protocol),
+ * key_window * variants may be 16 or 32 besides what is accepted without the flag (<= 8).  The reference protocol's
+ * phase leakage keeps more than 8 phases of one origin in flight from about its fourth round on (slow-set D = 8:
+ * 11 by round 5, 18 by round 9), so without the flag such runs stop with BRC_OVERFLOW.  The kernels are the ones an
+ * unflagged engine launches (their key-slot arithmetic is run-time); the flag lifts the host's limits, and a flagged
+ * engine at key_window * variants <= 8 runs exactly what an unflagged one runs.  It combines with
+ * BRC_FLAG_WIDE_RECORDS and BRC_FLAG_WIDE_VALUES.  Per instance the engine then holds NK * NPAD * 8 B of cells
+ * (NK = NPAD * key_window * variants key slots, NPAD = 128 or 256): 2 / 4 MB at NPAD 128 and 8 / 16 MB at NPAD 256
+ * for 16 / 32 slots per replica, plus 28 B (NPAD 128) or 44 B (NPAD 256) per key slot and the activity ring;
+ * an allocation that does not fit fails brc_create with BRC_E_NOMEM and the size.  One workgroup's LDS is 37-42 /
+ * 63-72 KB at NPAD 128 and 90-100 / 142-159 KB at NPAD 256, so three / two workgroups share a CU at NPAD 128 and
+ * one at NPAD 256.  Refused with
+ * BRC_E_INVALID and a reason: n <= 64 (the narrow kernels take windows up to 128 unflagged), BRC_MODE_SPEC (its
+ * per-phase windows stay <= 8), connection peers (five words per cell: they keep key_window * variants <= 8),
+ * key_window * variants > 32, and the one shape whose LDS carve exceeds a workgroup's 160 KB -- n > 128 with
+ * key_window = 32 under uniform or geometric delays with delay_max > 8 (164,016 B; 16 x 2 and 8 x 4 variants fit). */
+enum { BRC_FLAG_GENERAL_KEYS = 1, BRC_FLAG_WIDE_RECORDS = 2, BRC_FLAG_WIDE_VALUES = 4, BRC_FLAG_WIDE_WINDOWS = 8 };
 
 /* Injections may arrive between brc_run calls.  A record's time must not lie before the step its instance's wave
  * item stands at (brc_instance_result.t_now once the engine has run): t < t_now is BRC_E_STATE.  t == t_now is
