@@ -195,6 +195,9 @@ __device__ __forceinline__ uint32_t m_sender(uint64_t m) { return (uint32_t)((m 
 __device__ __forceinline__ uint32_t m_value(uint64_t m) { return (uint32_t)((m >> 56) & 0x7F); }
 // lean kernels: the LDS copy of a restricted-SEND key's metadata carries this bit (value ids are < 4)
 constexpr uint64_t M_RESTRICTED = 1ull << 63;
+// lean TYPED kernels (BRC_FRESH_SEND): the slot's HBM row has not been written since the slot was allocated; its
+// logical content is C32_FRESH in every lane.  LDS only, as M_RESTRICTED: the write-back masks it out
+constexpr uint64_t M_FRESH = 1ull << 62;
 __device__ __forceinline__ uint64_t m_pack(uint32_t s1, uint32_t tsend, uint32_t tquiet, uint32_t sender, uint32_t value) {
     return (uint64_t)(s1 & 0xFFFF) | ((uint64_t)(tsend & 0xFFFF) << 16) | ((uint64_t)(tquiet & 0xFFFF) << 32) |
            ((uint64_t)(sender & 0xFF) << 48) | ((uint64_t)(value & 0xFF) << 56);
@@ -365,6 +368,9 @@ __device__ __forceinline__ Ring16 ring_put(Ring16 r, uint32_t tl, uint32_t t, ui
 #ifndef BRC_OOBST
 #define BRC_OOBST 1          // lean kernels: the key loop's cell stores unconditional, kept words dropped out of range
 #endif
+#ifndef BRC_FRESH_SEND
+#define BRC_FRESH_SEND 1     // lean typed kernels: a new key's row is first written by its first SEND key-step (0: when allocated)
+#endif
 #ifndef BRC_PK
 #define BRC_PK 1             // lean kernels: a key pair's cell updates in the two 16-bit halves of a register
 #endif
@@ -427,6 +433,8 @@ void brc_step(const Params* __restrict__ pp) {
     constexpr bool SPEC = MODE == BRC_MODE_SPEC, BEB = MODE == BRC_MODE_BEB, CONN = MODE == KMODE_CONN;
     constexpr bool LEAN = lean_kernel<NPAD, MODE>();
     constexpr bool TYPED = typed_list(LEAN, EV, MODE);   // type-sorted key list, one pair body per class
+    // rows of new keys are left unwritten (M_FRESH) until their first SEND key-step or another access writes them
+    constexpr bool FRESH = BRC_FRESH_SEND && TYPED;
     static_assert(NLR == 0 || (LEAN && NLR == 2), "register delay masks: lean kernels, two delays");
     constexpr uint32_t CW = CONN ? 5 : 1;        // u64 words per cell (CONN: + ECHO and READY send rings)
     using T = typename MaskOf<NPAD>::type;
@@ -664,7 +672,7 @@ void brc_step(const Params* __restrict__ pp) {
     // rewrites those rows fresh (flush_clears) before anything reads them
     uint32_t clr = 0;
     auto flush_clears = [&]() {
-        if constexpr (LEAN) {
+        if constexpr (LEAN && !FRESH) {
             for (uint64_t b = __ballot(clr != 0); b; b &= b - 1) {
                 const int L = __ffsll((unsigned long long)b) - 1;
                 for (uint32_t cm = uni32((uint32_t)__builtin_amdgcn_readlane((int)clr, L)); cm; cm &= cm - 1) {
@@ -675,6 +683,33 @@ void brc_step(const Params* __restrict__ pp) {
             clr = 0;
         }
     };
+    // FRESH: no row is written when its slot is allocated (flush_clears does nothing).  The slot carries M_FRESH
+    // until the first SEND key-step stores the whole row (the key list's fresh class) or one of these two writes it
+    // C32_FRESH: fresh_row before anything else reads or partially writes the row of slot k (wave-uniform, every
+    // lane active), fresh_rows_all at the kernel's exit -- HBM between launches is what the eager fill leaves
+    auto fresh_row = [&](const uint32_t k) {
+        if constexpr (FRESH) {
+            if (k < NK) {
+                const uint64_t m = uni64(s_meta[k]);
+                if (m & M_FRESH) {
+                    cst(k, C32_FRESH);
+                    if (lane == 0) s_meta[k] = m & ~M_FRESH;
+                }
+            }
+        }
+    };
+    auto fresh_rows_all = [&]() {
+        if constexpr (FRESH) {
+            for (uint32_t w = 0; w < nkw; ++w) {
+                const uint64_t m = s_meta[w * 64 + lane];
+                uint64_t fb = __ballot((m & M_FRESH) != 0);
+                if (fb) {
+                    if (m & M_FRESH) s_meta[w * 64 + lane] = m & ~M_FRESH;
+                    for (; fb; fb &= fb - 1) cst(w * 64 + (uint32_t)__ffsll((unsigned long long)fb) - 1u, C32_FRESH);
+                }
+            }
+        }
+    };
     // lean: move the epoch to t - C32_KEEP when t is too far past it for a 7-bit offset.  Sends
     // before the new epoch are more than DM steps old and can no longer arrive: they become
     // C32_OLD (still "sent").  Only rows of slots holding a key.
@@ -682,7 +717,9 @@ void brc_step(const Params* __restrict__ pp) {
         if constexpr (LEAN) {
             const uint32_t nep = t - C32_KEEP, delta = nep - ep;
             for (uint32_t k = 0; k < NK; ++k) {
-                if (m_s1(uni64(s_meta[k])) == 0) continue;
+                const uint64_t mk = uni64(s_meta[k]);
+                if (m_s1(mk) == 0) continue;
+                if (FRESH && (mk & M_FRESH)) continue;   // unwritten: C32_FRESH holds no send step to move
                 const uint32_t c = cld(k);
                 uint32_t oE = (c >> C32_OE_SH) & 127u, oR = c >> C32_OR_SH;
                 if (oE < C32_OLD) oE = oE >= delta ? oE - delta : C32_OLD;
@@ -775,8 +812,9 @@ void brc_step(const Params* __restrict__ pp) {
         // a busy slot, or a phase index past this run's generation budget (brc_run): overflow
         if ((m_s1(m) != 0 && (t < m_tquiet(m) || (LEAN && ring_busy(k)))) || s >= P.s_limit) { ovf = true; return; }
         if (!LEAN) s_gen[mbase + k] = (uint16_t)(((s_gen[mbase + k] & GEN_MASK) + 1) & GEN_MASK);
-        if (LEAN) clr |= 1u << (s & Qm);                 // compact cells: the row is rewritten fresh
-        s_meta[mbase + k] = m_pack(s + 1, t, t + maxout, d, v);
+        if (LEAN && !FRESH) clr |= 1u << (s & Qm);       // compact cells: the row is rewritten fresh
+        // (FRESH: ... by its first SEND key-step; a slot reallocated while still unwritten simply stays so)
+        s_meta[mbase + k] = m_pack(s + 1, t, t + maxout, d, v) | (FRESH ? M_FRESH : 0ull);
         mark_lane(k, outset, BRC_SEND);
         q_until = max(q_until, t + maxout);
         st_msgs += n;
@@ -992,7 +1030,9 @@ void brc_step(const Params* __restrict__ pp) {
                 // a declared key holds its slot at least until the next step
                 if (!declared) { gen = (gen + 1) & GEN_MASK; tq = t + 1; fresh = true; }
                 if (is_send) tq = max(tq, t + hibit(os));
-                m = m_pack(r.s + 1, is_send ? t : NEVER, tq, r.node, (uint32_t)(uint8_t)r.value);
+                // FRESH: a (re)allocated slot's row is left unwritten; a declared key's SEND keeps the slot as it is
+                const uint64_t mf = FRESH ? (fresh ? M_FRESH : m & M_FRESH) : 0ull;
+                m = m_pack(r.s + 1, is_send ? t : NEVER, tq, r.node, (uint32_t)(uint8_t)r.value) | mf;
                 s_meta[mbase + k] = m;
                 const bool restricted = is_send && (r.dst & all64) != all64;
                 if (!LEAN) s_gen[mbase + k] = (uint16_t)(gen | (restricted ? GEN16_RESTRICTED : 0u));
@@ -1105,7 +1145,7 @@ void brc_step(const Params* __restrict__ pp) {
                     if (mine) q_until = max(q_until, t + hibit(os));
                 } else if (mine) {
                     const bool fresh = send_rec(r, os);
-                    if constexpr (LEAN) {
+                    if constexpr (LEAN && !FRESH) {
                         if (__ballot(fresh)) cst(uni32((uint32_t)r.slot), C32_FRESH);
                     }
                     q_until = max(q_until, t + hibit(os));
@@ -1181,6 +1221,8 @@ void brc_step(const Params* __restrict__ pp) {
                     }
                   }
                 } else {
+                    // msg_cell reads and rewrites one lane's word of the row: a whole row first (wave-uniform record)
+                    fresh_row(uni32((uint32_t)r.slot));
                     msg_marks(r, mine, (mine && d == r.node) ? msg_cell(r) : false);
                 }
             }
@@ -1263,9 +1305,11 @@ void brc_step(const Params* __restrict__ pp) {
             // k lands now at some receiver iff t - t_send is a delay of its sender's outset (reading the
             // next key word ahead measured no gain: A/B round 4)
             // this lane's slot of key word w: its type bits (0: not listed) and its list entry
+            uint64_t se_m = 0;                       // the metadata of the slot slot_entry looked at last
             auto slot_entry = [&](const uint32_t w, uint32_t& ent, bool& restr) -> uint32_t {
                 const uint64_t mE = uni64(s_act[(row * AT + 0) * nkw + w]), mR = uni64(s_act[(row * AT + 1) * nkw + w]);
                 const uint64_t m = s_meta[w * 64 + lane];
+                se_m = m;
                 const uint32_t dt = tsl - m_tsend(m);                      // the delay of a SEND landing now
                 bool sl;
                 if constexpr (NLR != 0) {
@@ -1295,7 +1339,10 @@ void brc_step(const Params* __restrict__ pp) {
             if constexpr (TYPED) {
                 // count per class first, scatter second (two passes over the key words): each segment in
                 // ascending slot order.  A restricted SEND, or a SEND beside ECHOs / READYs, is general.
+                // FRESH: the first SEND key-step of a slot whose row is still unwritten (M_FRESH) is class TCLS: it
+                // has no list segment, the scatter pass below performs it on the spot, with one row store
                 auto slot_class = [&](const uint32_t tb, const bool restr) -> uint32_t {
+                    if (FRESH && tb == TB_S && !restr && (se_m & M_FRESH)) return (uint32_t)TCLS;
                     return tb == TB_E ? 1u : tb == TB_R ? 2u : (tb == TB_S && !restr) ? 3u
                                                               : (BRC_TYPED_ER && tb == (TB_E | TB_R)) ? 4u : 0u;
                 };
@@ -1333,6 +1380,55 @@ void brc_step(const Params* __restrict__ pp) {
                         if (in) put_entry(spos[c] + below, ent);
                         spos[c] += (uint32_t)__popcll(bits);
                     });
+                    if constexpr (FRESH) {
+                        // this word's listed slots whose rows are unwritten.  Class TCLS (fs): the SEND stage of
+                        // process_pair applied to C32_FRESH has two outcomes per lane, so the row is stored whole
+                        // without being loaded -- receivers the SEND reaches now (hit, as there) get the ECHO entry
+                        // and their ECHO sent at this step, the others the fresh word; nothing is delivered.
+                        // Any other listed slot: its row is written C32_FRESH for the key loop to load.
+                        // (hit, the statistics and the ECHO ring marks restate process_pair's SEND stage by hand: a
+                        // change there has to be made here too)
+                        const bool fr = tb != 0 && (se_m & M_FRESH) != 0;
+                        const uint64_t fall = __ballot(fr);
+                        if (fall) {
+                            uint64_t fs = __ballot(fr && cl == (uint32_t)TCLS);
+                            if (fr) s_meta[w * 64 + lane] = se_m & ~M_FRESH;
+                            nk_lean += (uint32_t)__popcll(fs);
+                            for (uint64_t b = fall & ~fs; b; b &= b - 1)
+                                cst(w * 64 + (uint32_t)__ffsll((unsigned long long)b) - 1u, C32_FRESH);
+                            const uint32_t hitw = (SPEC ? F_ES : (F_EEX | F_ES)) | ((t - ep) << C32_OE_SH) | (C32_NEVER << C32_OR_SH);
+                            for (; fs; fs &= fs - 1) {
+                                const int sl = __ffsll((unsigned long long)fs) - 1;
+                                const uint64_t mk = readlane64(se_m, sl);
+                                const uint32_t snd = m_sender(mk) & 63u, dt = tsl - m_tsend(mk);
+                                bool hit;
+                                if constexpr (NLR != 0) {
+                                    hit = (((RL0 >> snd) & 1) != 0) == (dt == dly0);
+                                } else {
+                                    const uint32_t sj = popc(dset & ((1u << ((dt - 1u) & 31)) - 1u));
+                                    hit = (s_L[sj * 64 + lane] >> snd) & 1;
+                                }
+                                const uint64_t hm = __ballot(hit) & hon_mask;
+                                cst(w * 64 + (uint32_t)sl, lane_in(hm) ? hitw : C32_FRESH);
+                                st_cells += popc(hm);
+                                st_bcast += popc(hm);
+                                st_arr += lane_in(hm) ? 1u : 0u;
+                                // the ECHO ring marks of process_pair: rows t + every delay some sending lane has
+                                if constexpr (NLR != 0) {
+                                    const uint32_t mrow = ((t + ((lane & 1) ? dly1 : dly0)) & (RS - 1)) * AT * nkw;
+                                    if (lane < 2 && (hm & mk_ov) != 0)
+                                        atomicOr((unsigned long long*)&s_act[mrow + w], 1ull << sl);
+                                } else {
+                                    for (uint32_t ds = dset; ds; ds &= ds - 1) {
+                                        const uint32_t j = (uint32_t)__ffs(ds) - 1;
+                                        const uint32_t r = (t + j + 1u) & (RS - 1);
+                                        if ((hm & readlane64(outv, (int)j)) != 0 && lane == 0)
+                                            atomicOr((unsigned long long*)&s_act[(r * AT + 0) * nkw + w], 1ull << sl);
+                                    }
+                                }
+                            }
+                        }
+                    }
                 }
                 // segment padding -> the trash row (fewer than a chunk per class)
                 Unrolled<TCLS>::run([&](auto ci) {
@@ -2311,11 +2407,12 @@ void brc_step(const Params* __restrict__ pp) {
 #endif
 #undef BRC_STAMP
     // ---- write back
+    fresh_rows_all();                            // rows still unwritten: between launches HBM holds every row
     {
         const uint64_t mb = item * IPW * (uint64_t)NK;
         for (uint32_t i = lane; i < IPW * NK; i += 64) {
             if (item * IPW + i / NK < P.instances) {
-                gp(P.meta)[mb + i] = s_meta[i] & ~M_RESTRICTED;
+                gp(P.meta)[mb + i] = s_meta[i] & ~(M_RESTRICTED | (FRESH ? M_FRESH : 0ull));
                 gp(P.mgen)[mb + i] = LEAN ? ((s_meta[i] & M_RESTRICTED) ? GEN_RESTRICTED : 0u) : gen32(s_gen[i]);
             }
         }

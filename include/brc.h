@@ -241,7 +241,8 @@ typedef struct {
     uint64_t decide_rounds_sum;   /* sum of first-decide rounds over honest replicas */
     uint64_t max_t;
     uint64_t events_dropped;
-    uint64_t lane_loads;          /* cell words read (one per real lane per processed key-step) */
+    uint64_t lane_loads;          /* key-steps x lanes: one per real lane per processed key-step (lean kernels: wave-key-steps
+                                     x 64; a key's first SEND key-step counts although it stores its row without loading it) */
 } brc_stats;
 
 int brc_create(const brc_config* cfg, void** engine);

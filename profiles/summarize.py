@@ -12,7 +12,10 @@ HBM bytes follow MI355X_MICROARCH.md (rocprofv3 / HBM section): FETCH_SIZE and W
 in KiB and come from separate --pmc passes; on gfx950 FETCH_SIZE reports half the bytes of a
 coalesced streaming read, so it is doubled.  The kernel's cell loads are coalesced wave
 accesses of one cell per lane (8 B until r2e, 4 B since), where the doubling is checked against
-SQ_INSTS_VMEM_RD x 64 x cell bytes.
+SQ_INSTS_VMEM_RD x 64 x cell bytes.  Against the engine's own count the expectation is
+SQ_INSTS_VMEM_RD = lane_loads / 64 minus the fresh key-steps on the typed lean kernels (since
+BRC_FRESH_SEND a key's first SEND key-step stores its row without loading it, 19 % of cfg4's
+key-steps); lane_loads itself is wave-key-steps x 64 and did not change.
 """
 import csv
 import glob
