@@ -291,6 +291,12 @@ static int launch_step(int npad, int dm, bool events, int mode, bool wv4, bool r
     }
 }
 
+// the wide key-lifetime kernel (BRC_FLAG_WIDE_LIFE): one workgroup of NPAD threads per instance
+static int launch_life_wide(int npad, int mode, uint32_t blocks, uint32_t lds, hipStream_t st, const Params* P) {
+    return npad == 128 ? launch_life_128(mode, blocks, lds, st, P)
+         : npad == 256 ? launch_life_256(mode, blocks, lds, st, P) : BRC_E_INVALID;
+}
+
 static void free_all(Engine* e) {
     void* ps[] = {e->cells, e->meta, e->mgen, e->kdst, e->act, e->actany, e->items, e->inst, e->istats,
                   e->cons0, e->cons1, e->hmask, e->inj, e->inj_off, e->inj_cnt, e->byz, e->prop, e->events,
@@ -355,7 +361,7 @@ static int clear_state(Engine* e, bool full) {
     HIPCHK(e, hipMemsetAsync(e->istats, 0, (size_t)e->cfg.instances * 4 * 8, e->stream));
     HIPCHK(e, hipMemsetAsync(e->cons0, 0, (size_t)e->nitems * e->lpi * 8, e->stream));
     HIPCHK(e, hipMemsetAsync(e->cons1, 0, (size_t)e->nitems * e->lpi * 8, e->stream));
-    HIPCHK(e, hipMemsetAsync(e->hmask, 0, (size_t)e->nitems * e->cons_bytes, e->stream));
+    if (e->cons_bytes) HIPCHK(e, hipMemsetAsync(e->hmask, 0, (size_t)e->nitems * e->cons_bytes, e->stream));
     HIPCHK(e, hipMemsetAsync(e->gcount, 0, 8 * 8, e->stream));
     if ((!e->compact && !e->wide) || e->wide_rec) HIPCHK(e, hipMemsetAsync(e->xsn, 0, (size_t)e->nitems * 4, e->stream));
     if (e->event_count) HIPCHK(e, hipMemsetAsync(e->event_count, 0, 8, e->stream));
@@ -457,7 +463,7 @@ int brc_create(const brc_config* cfg, void** out) {
         (c.byz_pattern != BRC_BYZ_NONE && c.byz_pattern != BRC_BYZ_EQUIVOCATE) ||
         c.proposals > BRC_PROPOSALS_LOADED || c.mode > BRC_MODE_BEB ||
         (c.flags & ~(uint32_t)(BRC_FLAG_GENERAL_KEYS | BRC_FLAG_WIDE_RECORDS | BRC_FLAG_WIDE_VALUES |
-                               BRC_FLAG_WIDE_WINDOWS)) ||
+                               BRC_FLAG_WIDE_WINDOWS | BRC_FLAG_WIDE_LIFE)) ||
         // the general form at NPAD = 64 with sender peers is the reference protocol's (KMODE_XREF)
         ((c.flags & BRC_FLAG_GENERAL_KEYS) && c.n > 32 && c.n <= 64 && c.peer_mode == BRC_PEER_SENDER &&
          c.mode != BRC_MODE_REFERENCE) ||
@@ -488,6 +494,30 @@ int brc_create(const brc_config* cfg, void** out) {
                                                : "BRC_FLAG_WIDE_WINDOWS needs sender peers: the connection-peer wide kernels "
                                                  "(five words per cell) keep key_window * variants <= 8";
         return BRC_E_INVALID;
+    }
+    if (c.flags & BRC_FLAG_WIDE_LIFE) {
+        // the wide key-lifetime kernel (brc_life_wide.h): every field it cannot serve is named
+        const char* kv = getenv("BRC_KERNEL");
+        const char* why =
+            c.n <= 64 ? "BRC_FLAG_WIDE_LIFE is for n > 64: at n in 33..64 the key-lifetime kernel runs without a flag"
+            : c.peer_mode != BRC_PEER_SENDER ? "BRC_FLAG_WIDE_LIFE needs sender peers (peer_mode): the wide key-lifetime kernel "
+                                               "has no connection-peer form"
+            : c.protocol != BRC_PROTO_CONSENSUS ? "BRC_FLAG_WIDE_LIFE needs the consensus protocol (protocol): the kernel takes no "
+                                                  "injections, and a broadcast run is made of them"
+            : c.proposals == BRC_PROPOSALS_NONE ? "BRC_FLAG_WIDE_LIFE needs Philox or loaded proposals (proposals)"
+            : (c.delay_model != BRC_DELAY_CONST && c.delay_model != BRC_DELAY_SLOWSET)
+                ? "BRC_FLAG_WIDE_LIFE needs constant or slow-set delays (delay_model): uniform / geometric delays have no "
+                  "two-class form"
+            : c.delay_max > 8 ? "BRC_FLAG_WIDE_LIFE needs delay_max <= 8 (a key's life must fit the 32-step ring)"
+            : c.event_capacity != 0 ? "BRC_FLAG_WIDE_LIFE: no event log (event_capacity): the kernel visits no single message"
+            : c.byz_pattern != BRC_BYZ_NONE ? "BRC_FLAG_WIDE_LIFE: no byz_pattern (a pattern is made of injections); silent "
+                                              "Byzantine replicas go through byzantine_mask / brc_load_byzantine"
+            : (c.flags & (BRC_FLAG_WIDE_RECORDS | BRC_FLAG_WIDE_VALUES))
+                ? "BRC_FLAG_WIDE_LIFE: not with BRC_FLAG_WIDE_RECORDS / BRC_FLAG_WIDE_VALUES (flags), which select the step "
+                  "kernel's record and 3-bit forms"
+            : (kv && strcmp(kv, "step") == 0) ? "BRC_FLAG_WIDE_LIFE with BRC_KERNEL=step: a lifetime-only engine has no step state"
+                                              : nullptr;
+        if (why) { g_create_err = why; return BRC_E_INVALID; }
     }
     Engine* e = new Engine();
     e->cfg = c;
@@ -582,6 +612,21 @@ int brc_create(const brc_config* cfg, void** out) {
                   "(consensus, Philox / loaded proposals, delay_max <= 8, constant or slow-set delays, no event log)"
                 : "the step kernel's cells do not fit in free device memory and the key-lifetime kernel cannot run "
                   "this configuration";
+            delete e;
+            return BRC_E_INVALID;
+        }
+    }
+    if (c.flags & BRC_FLAG_WIDE_LIFE) {
+        // lifetime-only, as the "big" engines above: no cells, key-slot arrays or activity ring
+        e->life_pl = false;
+        e->life_rw = LIFE_RW;
+        e->life_lds = lds_bytes_life_wide(e->npad, e->NK, e->nkw, spec, c.key_window);
+        e->life_cfg = true;
+        e->step_ok = false;
+        e->cons_bytes = 0;                               // the host masks / phase counters live in LDS for the whole run
+        if (e->life_lds > 160 * 1024) {
+            g_create_err = "BRC_FLAG_WIDE_LIFE: key_window * variants = " + std::to_string(c.key_window * c.variants) +
+                           " exceeds the wide key-lifetime kernel's LDS (lds " + std::to_string(e->life_lds) + " B of 163840)";
             delete e;
             return BRC_E_INVALID;
         }
@@ -698,6 +743,10 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
     if (!e || (!list && count)) return BRC_E_INVALID;
     if (e->pattern_active) { e->err = "explicit injections cannot be combined with byz_pattern"; return BRC_E_STATE; }
     const brc_config& c = e->cfg;
+    if (!e->step_ok && count && e->wide) {
+        e->err = "this engine runs on the wide key-lifetime kernel only (BRC_FLAG_WIDE_LIFE): no injections";
+        return BRC_E_UNSUPPORTED;
+    }
     if (!e->step_ok && count) {
         e->err = "this engine runs on the key-lifetime kernel only (its step-kernel state does not fit the device, "
                  "or a key window above 32 at n in 33..64 with sender peers, of 128 with connection peers): no injections";
@@ -1036,6 +1085,11 @@ int brc_run(void* h, uint32_t max_steps, uint32_t* running_left) {
     }
     int rc = upload_injections(e);
     if (rc) return rc;
+    if (!life && !e->step_ok && e->wide) {
+        e->err = "this engine runs on the wide key-lifetime kernel only (BRC_FLAG_WIDE_LIFE): a fresh run to completion, "
+                 "no injections, max_steps = 0 (brc_reset first)";
+        return BRC_E_UNSUPPORTED;
+    }
     if (!life && !e->step_ok) {
         e->err = "this engine runs on the key-lifetime kernel only (its step-kernel state does not fit, or a key "
                  "window above 32 at n in 33..64 with sender peers, of 128 with connection peers): a fresh run to "
@@ -1091,7 +1145,10 @@ int brc_run(void* h, uint32_t max_steps, uint32_t* running_left) {
     const int kmode = c.peer_mode == BRC_PEER_CONNECTION ? KMODE_CONN : e->general ? KMODE_XREF : (int)c.mode;
     e->fresh = false;
     e->last_life = life;
-    if (life) {
+    if (life && e->wide) {
+        rc = launch_life_wide(e->npad, kmode, (uint32_t)e->nitems, e->life_lds, e->stream, e->dparams);
+        e->life_done = true;
+    } else if (life) {
         rc = launch_life(kmode, e->life_pl, e->life_rw == LIFE_RW16, c.key_window >= 64,
                          life_hbm_meta(c.key_window, e->life_pl), (uint32_t)e->nitems,
                          e->life_lds, e->stream, e->dparams);

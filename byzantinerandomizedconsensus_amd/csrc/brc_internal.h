@@ -291,6 +291,20 @@ constexpr uint32_t LIFE_RW16 = 64;
 int launch_life(int mode, bool perlink, bool dm16, bool qbig, bool hm, uint32_t blocks, uint32_t lds, hipStream_t s,
                 const Params* P);
 
+// Wide key-lifetime kernel (brc_life_wide.h, BRC_FLAG_WIDE_LIFE: n > 64, two-class delays, sender peers): bytes of
+// dynamic LDS one workgroup needs (must match the kernel's carve):
+//   kab[nkw][2] u64 (a step's class bitmaps per key word) | consensus area (cons_words_wide: REFERENCE / BEB host
+//   masks hm[4][NW][NPAD] u64, SPEC cnt[Q][NPAD] u32) | meta[NK] u32 | rg[4][LIFE_RW] u32 (the step-statistics
+//   rings) | ctl[16] u32 (rows, class sizes, reduction slots) | dA[NK], dB[NK] u8 (class delivery steps) |
+//   sq[Q][NPAD] u8 (deferred SENDs)
+__host__ __device__ inline uint32_t lds_bytes_life_wide(int npad, uint32_t NK, uint32_t nkw, bool spec, uint32_t Q) {
+    return 16 * nkw + 8 * cons_words_wide(spec, (uint32_t)npad, Q) + 4 * NK + 4 * (4 * LIFE_RW + 16) + 2 * NK +
+           Q * (uint32_t)npad;
+}
+// ... its launchers, one translation unit per NPAD (brc_kern_life128.hip / brc_kern_life256.hip); mode: BRC_MODE_*
+int launch_life_128(int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
+int launch_life_256(int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
+
 // Step-kernel launchers, one translation unit per replica-set width NPAD (brc_kern_<NPAD>.hip).
 // Return 0 on success, BRC_E_INVALID when no instantiation matches (dm), BRC_E_HIP on a launch error.
 int launch_step_4(int dm, bool events, int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);

@@ -28,6 +28,8 @@ Workloads:
              -wval: the same under BRC_FLAG_WIDE_VALUES (three-bit value ids), binary proposals
   cfg5-ref-slow-q16  the same committee to round cap 6 through a key window of 16 (BRC_FLAG_WIDE_WINDOWS), 384
              instances per GPU (informational: no earlier build runs it)
+  cfg5-const-life, cfg5-ref-slow-life, cfg5-ref-slow-q16-life  their step rows' dictionaries plus BRC_FLAG_WIDE_LIFE (the
+             wide key-lifetime kernel); cfg5-ref-slow-q16-life-6144: the q16 run at 6144 instances (informational)
 
 A step is one pass of the hot path over the batch (reset + run to completion); the timed region
 is K steps between barriers, max over ranks.  `roofline.achieved` = this layout's algorithmic
@@ -124,6 +126,13 @@ def workloads(L):
     # ... to round cap 6 through a key window of 16 (BRC_FLAG_WIDE_WINDOWS; 8 MB of cells per instance): without the
     # flag brc_create refuses the window, and at window 8 the run stops with BRC_OVERFLOW around its fourth round
     W["cfg5-ref-slow-q16"] = (384, True, dict(W["cfg5-ref-slow"][2], round_cap=6, key_window=16, wide_windows=True))
+    # the two-class rows above on the wide key-lifetime kernel (BRC_FLAG_WIDE_LIFE: no cells, csrc/brc_life_wide.h),
+    # informational: the same dictionaries plus the flag, so a row and its -life twin count the same cell-steps
+    for name in ("cfg5-const", "cfg5-ref-slow", "cfg5-ref-slow-q16"):
+        W[name + "-life"] = (W[name][0], True, dict(W[name][2], wide_life=True))
+    # ... and the q16 run at cfg5's batch: 8 MB of cells per instance cap the step kernel at 384 instances, the
+    # lifetime kernel allocates none
+    W["cfg5-ref-slow-q16-life-6144"] = (6144, True, dict(W["cfg5-ref-slow-q16-life"][2]))
     return W
 
 
@@ -200,7 +209,7 @@ def roofline(name, n, bpc, cell_steps, kernel_ms, peer_mode=0, kernel="step"):
     if kernel not in ("step", "life"):
         raise ValueError("%s: launches ran different kernels (%r); report them apart" % (name, kernel))
     if kernel == "life":
-        out = {"bound": "issue", "kernel": "brc_life", "unit": "GB/s", "peak": HBM_PEAK_GBS, "achieved": None,
+        out = {"bound": "issue", "kernel": "brc_life" if n <= 64 else "brc_life_wide", "unit": "GB/s", "peak": HBM_PEAK_GBS, "achieved": None,
                "frac": None, "survey_model_gbs": bpc * cell_steps / sec / 1e9,
                "cell_steps_per_s": cell_steps / sec, "traffic": None, "traffic_frac": None,
                "note": "key-lifetime kernel: cells stay in registers for a key's lifetime, no HBM cell traffic "

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define BRC_ABI_VERSION 10
+#define BRC_ABI_VERSION 11
 
 enum {
     BRC_OK = 0,
@@ -143,8 +143,31 @@ typedef struct {
  * BRC_E_INVALID and a reason: n <= 64 (the narrow kernels take windows up to 128 unflagged), BRC_MODE_SPEC (its
  * per-phase windows stay <= 8), connection peers (five words per cell: they keep key_window * variants <= 8),
  * key_window * variants > 32, and the one shape whose LDS carve exceeds a workgroup's 160 KB -- n > 128 with
- * key_window = 32 under uniform or geometric delays with delay_max > 8 (164,016 B; 16 x 2 and 8 x 4 variants fit). */
-enum { BRC_FLAG_GENERAL_KEYS = 1, BRC_FLAG_WIDE_RECORDS = 2, BRC_FLAG_WIDE_VALUES = 4, BRC_FLAG_WIDE_WINDOWS = 8 };
+ * key_window = 32 under uniform or geometric delays with delay_max > 8 (164,016 B; 16 x 2 and 8 x 4 variants fit).
+ * BRC_FLAG_WIDE_LIFE (v11): at n > 64, run the wide key-lifetime kernel (csrc/brc_life_wide.h) instead of the wide
+ * step kernel.  Under constant and slow-set delays a key's whole life is two receiver-class states (honest fast
+ * receivers, honest slow ones), simulated in closed form when the key is created, so the engine keeps no cells: per
+ * instance it holds 16 B * NPAD of consensus records and about 100 B, where the step kernel holds NK * NPAD * 8 B of
+ * cells (4 / 8 / 16 MB at NPAD 256 for windows 8 / 16 / 32).  Such an engine is lifetime-only, like the engines at
+ * n <= 64 whose step state does not fit (brc_last_kernel, below): brc_last_kernel reports BRC_KERNEL_LIFE before and
+ * after the run; brc_inject, and brc_run with max_steps > 0, return BRC_E_UNSUPPORTED and name the kernel;
+ * brc_reset, brc_reset_at, brc_load_proposals, brc_load_byzantine and every reader work as on any engine.  Results
+ * are the step kernel's, field for field.  BRC_OVERFLOW when an origin's window is full (a SEND would reuse a slot
+ * whose key still has arrivals ahead) or a replica starts more than min(key_window, 32) SENDs in one step, step-cap
+ * stops (BRC_STEPCAP once the next step with arrivals lies past step_cap) and t_stop (the last step <= the stop at
+ * which an honest cell had an arrival) behave as on the narrow key-lifetime kernel and the step kernels.
+ * Eligible: sender peers, the consensus protocol, BRC_MODE_REFERENCE, BRC_MODE_SPEC (variants = 1) or BRC_MODE_BEB,
+ * Philox or loaded proposals (value ids <= 3), BRC_DELAY_CONST or BRC_DELAY_SLOWSET with delay_max <= 8, no event
+ * log, no byz_pattern (silent Byzantine replicas through byzantine_mask / byzantine_mask_hi / brc_load_byzantine),
+ * key_window * variants <= 8, or 16 / 32 together with BRC_FLAG_WIDE_WINDOWS (REFERENCE / BEB).  One workgroup's LDS is
+ * 16 / 24 / 38 KB at NPAD 128 and 47 / 62 / 91 KB at NPAD 256 for windows 8 / 16 / 32 (SPEC, window 8: 12 / 23 KB).
+ * Anything else with the flag set fails brc_create with BRC_E_INVALID and a reason naming the field: n <= 64,
+ * connection peers, the broadcast protocol, no proposals, uniform / geometric delays, delay_max > 8, an event log, a
+ * pattern, BRC_FLAG_WIDE_RECORDS / BRC_FLAG_WIDE_VALUES (they select the step kernel's record / 3-bit forms), an LDS
+ * carve above 160 KB, and BRC_KERNEL=step in the environment (a lifetime-only engine has no step state).  Without
+ * the flag nothing changes: BRC_KERNEL=life at n > 64 still runs the step kernel. */
+enum { BRC_FLAG_GENERAL_KEYS = 1, BRC_FLAG_WIDE_RECORDS = 2, BRC_FLAG_WIDE_VALUES = 4, BRC_FLAG_WIDE_WINDOWS = 8,
+       BRC_FLAG_WIDE_LIFE = 16 };
 
 /* Injections may arrive between brc_run calls.  A record's time must not lie before the step its instance's wave
  * item stands at (brc_instance_result.t_now once the engine has run): t < t_now is BRC_E_STATE.  t == t_now is
