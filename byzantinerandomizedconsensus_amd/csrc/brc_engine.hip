@@ -292,7 +292,10 @@ static int launch_step(int npad, int dm, bool events, int mode, bool wv4, bool r
 }
 
 // the wide key-lifetime kernel (BRC_FLAG_WIDE_LIFE): one workgroup of NPAD threads per instance
-static int launch_life_wide(int npad, int mode, uint32_t blocks, uint32_t lds, hipStream_t st, const Params* P) {
+// pat: its pattern form (BRC_FLAG_LIFE_PATTERN)
+static int launch_life_wide(int npad, int mode, bool pat, uint32_t blocks, uint32_t lds, hipStream_t st, const Params* P) {
+    if (pat) return npad == 128 ? launch_life_128p(mode, blocks, lds, st, P)
+                  : npad == 256 ? launch_life_256p(mode, blocks, lds, st, P) : BRC_E_INVALID;
     return npad == 128 ? launch_life_128(mode, blocks, lds, st, P)
          : npad == 256 ? launch_life_256(mode, blocks, lds, st, P) : BRC_E_INVALID;
 }
@@ -404,6 +407,8 @@ static int upload_injections(Engine* e) {
 
 static int apply_pattern(Engine* e) {
     if (e->cfg.byz_pattern != BRC_BYZ_EQUIVOCATE) return BRC_OK;
+    // BRC_FLAG_LIFE_PATTERN: the wide key-lifetime kernel reads the Byzantine mask itself, no injection list
+    if (e->cfg.flags & BRC_FLAG_LIFE_PATTERN) return BRC_OK;
     const uint32_t cap = (uint32_t)e->ipw * 6u * e->cfg.n;   // worst case: every replica Byzantine
     const size_t total = (size_t)e->nitems * cap;
     if (total > e->inj_capacity) {
@@ -445,6 +450,23 @@ int brc_create(const brc_config* cfg, void** out) {
     if (!cfg || !out) { g_create_err = "null argument"; return BRC_E_INVALID; }
     *out = nullptr;
     const brc_config& c = *cfg;
+    if (c.flags & BRC_FLAG_LIFE_PATTERN) {
+        // the equivocation pattern on the wide key-lifetime kernel (brc_life_wide.h PAT): what the flag needs besides
+        // BRC_FLAG_WIDE_LIFE's own conditions (below).  First, so that each of these gets its reason
+        const char* why =
+            !(c.flags & BRC_FLAG_WIDE_LIFE) ? "BRC_FLAG_LIFE_PATTERN needs BRC_FLAG_WIDE_LIFE (flags): it selects the wide "
+                                              "key-lifetime kernel's pattern form"
+            : c.n <= 64 ? "BRC_FLAG_LIFE_PATTERN is for n > 64: at n <= 64 a byz_pattern runs on the step kernel"
+            : c.peer_mode != BRC_PEER_SENDER ? "BRC_FLAG_LIFE_PATTERN needs sender peers (peer_mode)"
+            : c.mode == BRC_MODE_SPEC ? "BRC_FLAG_LIFE_PATTERN: not with BRC_MODE_SPEC (mode), which has variants = 1 above 64 "
+                                        "replicas and so cannot carry the pattern's two keys per origin"
+            : c.byz_pattern != BRC_BYZ_EQUIVOCATE ? "BRC_FLAG_LIFE_PATTERN needs byz_pattern = BRC_BYZ_EQUIVOCATE: without a "
+                                                    "pattern BRC_FLAG_WIDE_LIFE alone runs the same committee"
+            : (c.variants != 2 && c.variants != 4) ? "BRC_FLAG_LIFE_PATTERN needs variants = 2 or 4: the pattern's keys are "
+                                                     "variants 0 and 1 of a Byzantine origin"
+                                                   : nullptr;
+        if (why) { g_create_err = why; return BRC_E_INVALID; }
+    }
     if (c.n < 1 || c.n > 256 || c.instances == 0 || c.delay_max < 1 || c.delay_max > 16 ||
         c.step_cap > STEP_LIMIT || c.peer_mode > BRC_PEER_CONNECTION ||
         (c.peer_mode == BRC_PEER_CONNECTION && c.mode != BRC_MODE_REFERENCE) ||
@@ -463,7 +485,7 @@ int brc_create(const brc_config* cfg, void** out) {
         (c.byz_pattern != BRC_BYZ_NONE && c.byz_pattern != BRC_BYZ_EQUIVOCATE) ||
         c.proposals > BRC_PROPOSALS_LOADED || c.mode > BRC_MODE_BEB ||
         (c.flags & ~(uint32_t)(BRC_FLAG_GENERAL_KEYS | BRC_FLAG_WIDE_RECORDS | BRC_FLAG_WIDE_VALUES |
-                               BRC_FLAG_WIDE_WINDOWS | BRC_FLAG_WIDE_LIFE)) ||
+                               BRC_FLAG_WIDE_WINDOWS | BRC_FLAG_WIDE_LIFE | BRC_FLAG_LIFE_PATTERN)) ||
         // the general form at NPAD = 64 with sender peers is the reference protocol's (KMODE_XREF)
         ((c.flags & BRC_FLAG_GENERAL_KEYS) && c.n > 32 && c.n <= 64 && c.peer_mode == BRC_PEER_SENDER &&
          c.mode != BRC_MODE_REFERENCE) ||
@@ -510,8 +532,9 @@ int brc_create(const brc_config* cfg, void** out) {
                   "two-class form"
             : c.delay_max > 8 ? "BRC_FLAG_WIDE_LIFE needs delay_max <= 8 (a key's life must fit the 32-step ring)"
             : c.event_capacity != 0 ? "BRC_FLAG_WIDE_LIFE: no event log (event_capacity): the kernel visits no single message"
-            : c.byz_pattern != BRC_BYZ_NONE ? "BRC_FLAG_WIDE_LIFE: no byz_pattern (a pattern is made of injections); silent "
-                                              "Byzantine replicas go through byzantine_mask / brc_load_byzantine"
+            : (c.byz_pattern != BRC_BYZ_NONE && !(c.flags & BRC_FLAG_LIFE_PATTERN))
+                ? "BRC_FLAG_WIDE_LIFE: no byz_pattern (a pattern is made of injections); silent "
+                  "Byzantine replicas go through byzantine_mask / brc_load_byzantine"
             : (c.flags & (BRC_FLAG_WIDE_RECORDS | BRC_FLAG_WIDE_VALUES))
                 ? "BRC_FLAG_WIDE_LIFE: not with BRC_FLAG_WIDE_RECORDS / BRC_FLAG_WIDE_VALUES (flags), which select the step "
                   "kernel's record and 3-bit forms"
@@ -620,7 +643,8 @@ int brc_create(const brc_config* cfg, void** out) {
         // lifetime-only, as the "big" engines above: no cells, key-slot arrays or activity ring
         e->life_pl = false;
         e->life_rw = LIFE_RW;
-        e->life_lds = lds_bytes_life_wide(e->npad, e->NK, e->nkw, spec, c.key_window);
+        e->life_lds = lds_bytes_life_wide(e->npad, e->NK, e->nkw, spec, c.key_window,
+                                          (c.flags & BRC_FLAG_LIFE_PATTERN) != 0);
         e->life_cfg = true;
         e->step_ok = false;
         e->cons_bytes = 0;                               // the host masks / phase counters live in LDS for the whole run
@@ -1146,7 +1170,8 @@ int brc_run(void* h, uint32_t max_steps, uint32_t* running_left) {
     e->fresh = false;
     e->last_life = life;
     if (life && e->wide) {
-        rc = launch_life_wide(e->npad, kmode, (uint32_t)e->nitems, e->life_lds, e->stream, e->dparams);
+        rc = launch_life_wide(e->npad, kmode, (c.flags & BRC_FLAG_LIFE_PATTERN) != 0, (uint32_t)e->nitems, e->life_lds,
+                              e->stream, e->dparams);
         e->life_done = true;
     } else if (life) {
         rc = launch_life(kmode, e->life_pl, e->life_rw == LIFE_RW16, c.key_window >= 64,

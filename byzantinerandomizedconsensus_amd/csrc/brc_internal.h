@@ -297,13 +297,20 @@ int launch_life(int mode, bool perlink, bool dm16, bool qbig, bool hm, uint32_t 
 //   masks hm[4][NW][NPAD] u64, SPEC cnt[Q][NPAD] u32) | meta[NK] u32 | rg[4][LIFE_RW] u32 (the step-statistics
 //   rings) | ctl[16] u32 (rows, class sizes, reduction slots) | dA[NK], dB[NK] u8 (class delivery steps) |
 //   sq[Q][NPAD] u8 (deferred SENDs)
-__host__ __device__ inline uint32_t lds_bytes_life_wide(int npad, uint32_t NK, uint32_t nkw, bool spec, uint32_t Q) {
+// pat (the pattern form, BRC_FLAG_LIFE_PATTERN): four class bitmaps per key word instead of two (+ 16 nkw), and
+//   pbyz[4] u64 (the Byzantine mask) | pcnt[8] u32 (class sizes per parity) | oA[2 NPAD], oB[2 NPAD] u8 (the
+//   out-classes' delivery steps of the pattern keys)
+__host__ __device__ inline uint32_t lds_bytes_life_wide(int npad, uint32_t NK, uint32_t nkw, bool spec, uint32_t Q,
+                                                        bool pat = false) {
     return 16 * nkw + 8 * cons_words_wide(spec, (uint32_t)npad, Q) + 4 * NK + 4 * (4 * LIFE_RW + 16) + 2 * NK +
-           Q * (uint32_t)npad;
+           Q * (uint32_t)npad + (pat ? 16 * nkw + 64 + 4 * (uint32_t)npad : 0u);
 }
 // ... its launchers, one translation unit per NPAD (brc_kern_life128.hip / brc_kern_life256.hip); mode: BRC_MODE_*
 int launch_life_128(int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
 int launch_life_256(int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
+// ... and of the pattern form (brc_kern_life128p.hip / brc_kern_life256p.hip); mode: BRC_MODE_REFERENCE / BRC_MODE_BEB
+int launch_life_128p(int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
+int launch_life_256p(int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
 
 // Step-kernel launchers, one translation unit per replica-set width NPAD (brc_kern_<NPAD>.hip).
 // Return 0 on success, BRC_E_INVALID when no instantiation matches (dm), BRC_E_HIP on a launch error.

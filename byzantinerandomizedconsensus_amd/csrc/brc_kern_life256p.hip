@@ -1,0 +1,10 @@
+// brc_kern_life256p.hip -- the NPAD = 256 wide key-lifetime kernel in its pattern form (BRC_FLAG_LIFE_PATTERN;
+// brc_life_wide.h PAT), one instantiation per protocol mode that has two key variants (REFERENCE, BEB).  A unit of
+// its own: the other units compile what they did.
+#include "brc_life_wide.h"
+
+namespace brc {
+int launch_life_256p(int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P) {
+    return launch_life_wide_pat_npad<256>(mode, blocks, lds, s, P);
+}
+}  // namespace brc

@@ -28,6 +28,19 @@
 // injections, a fresh engine run to completion.  Overflow (an origin's window full, more than min(Q, SENDQ_MAX)
 // SENDs of one replica in one step), step-cap stops and t_stop behave as in brc_life.h.  Results are identical to the
 // wide step kernel's (tests/test_gpu_wide_life.py checks both against the C oracle).
+//
+// PAT (BRC_FLAG_LIFE_PATTERN): the even / odd equivocation pattern (BRC_BYZ_EQUIVOCATE; brc_engine.hip
+// expand_equivocate) as a function of the instance's Byzantine mask, with no injection.  Byzantine replica b declares
+// the keys (b NV + v, s = 0) with value id 1 + v (v = 0, 1), SENDs key v at t = 0 to the replicas of parity v, and
+// ECHOes and READYs both keys to everyone at t = 1.  Such a key's life is four receiver-class states -- (fast | slow)
+// x (got the SEND: "in" | did not: "out") -- plus the origin's own ECHO and READY, one arrival each at
+// 1 + delay(b -> class).  At t = 0 every Byzantine lane (idle otherwise) simulates its two keys with
+// simulate_pattern, the four-class form of simulate_batch; honest keys keep the two-class form.  A replica's class
+// for a pattern key depends on its parity, so the PAT form keeps four class bitmaps per key word (fast even, slow
+// even, fast odd, slow odd) and the out-classes' delivery steps in a side table oA / oB[2 NPAD] (entry 2 b + v: only
+// phase slot 0 of variants 0 / 1 of a Byzantine origin is ever a pattern key).  Step 1 is entered although nothing
+// may arrive then: it is the step of the pattern's second action, as in the oracle.  The PAT = false instantiations
+// compile to what they did.
 #pragma once
 #include "brc_life.h"
 
@@ -37,12 +50,14 @@
 
 namespace brc {
 
-template <int NPAD, int MODE>
+template <int NPAD, int MODE, bool PAT = false>
 __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const Params* __restrict__ pp) {
     const Params& P = *pp;
     constexpr bool SPEC = MODE == BRC_MODE_SPEC, BEB = MODE == BRC_MODE_BEB, CONN = false;   // (brc_life_cell.h reads all three)
     static_assert(NPAD == 128 || NPAD == 256, "wide committees: two or four waves");
     static_assert(MODE == BRC_MODE_REFERENCE || MODE == BRC_MODE_SPEC || MODE == BRC_MODE_BEB, "sender peers");
+    static_assert(!PAT || MODE != BRC_MODE_SPEC, "the pattern needs two key variants: SPEC above 64 replicas has one");
+    constexpr uint32_t KC = PAT ? 4u : 2u;           // class bitmaps per key word
     constexpr uint32_t NW = NPAD / 64;
     constexpr uint32_t RW = LIFE_RW;                 // ring rows (> the longest key lifetime, 4 Dd <= 32)
     extern __shared__ __attribute__((aligned(16))) uint64_t smem[];
@@ -56,8 +71,9 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
 
     // ---- LDS carve (lds_bytes_life_wide): kab[nkw][2] u64 | consensus area (REFERENCE / BEB hm[4][NW][NPAD] u64,
     // SPEC cnt[Q][NPAD] u32) | meta[NK] u32 | rg[4][RW] u32 | ctl[16] u32 | dA[NK], dB[NK] u8 | sq[Q][NPAD] u8
+    // PAT: kab[nkw][4], and after sq: pbyz[4] u64 | pcnt[8] u32 | oA[2 NPAD], oB[2 NPAD] u8
     uint64_t* const s_kab = smem;                    // the step's consumed class bitmaps per key word: class A, class B
-    uint64_t* const s_hm = s_kab + 2 * nkw;
+    uint64_t* const s_hm = s_kab + KC * nkw;
     uint32_t* const s_cnt = (uint32_t*)s_hm;
     uint32_t* const s_meta = (uint32_t*)(s_hm + cons_words_wide(SPEC, NPAD, Q));
     uint32_t* const s_rg = s_meta + NK;              // arrivals [RW] | messages [RW] | cells [RW] | deliveries [RW]
@@ -67,6 +83,11 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
     uint8_t* const s_dA = (uint8_t*)(s_ctl + 16);    // class delivery steps (brc_life.h: 0x80 | step mod 128, 0: none)
     uint8_t* const s_dB = s_dA + NK;
     uint8_t* const s_sq = s_dB + NK;                 // deferred SENDs: values (phase indices consecutive)
+    uint64_t* const s_pbyz = (uint64_t*)(s_sq + Q * NPAD);   // PAT: the instance's Byzantine mask words
+    // PAT: [0..3] honest fast even / fast odd / slow even / slow odd replicas [4] Byzantine replicas
+    uint32_t* const s_pcnt = (uint32_t*)(s_pbyz + 4);
+    uint8_t* const s_oA = (uint8_t*)(s_pcnt + 8);    // PAT: out-class delivery steps of pattern key 2 b + v (as dA / dB)
+    uint8_t* const s_oB = s_oA + 2 * NPAD;
 
     const uint32_t d = tid;
     const uint64_t g = P.inst_offset + inst;
@@ -87,12 +108,17 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
 
     // ---- LDS init
     for (uint32_t i = d; i < NK; i += NPAD) { s_meta[i] = 0u; s_dA[i] = 0; s_dB[i] = 0; }
-    for (uint32_t i = d; i < 2 * nkw; i += NPAD) s_kab[i] = 0ull;
+    for (uint32_t i = d; i < KC * nkw; i += NPAD) s_kab[i] = 0ull;
     for (uint32_t i = d; i < 4 * RW + 16; i += NPAD) s_rg[i] = 0u;     // the rings and ctl
     if constexpr (SPEC) {
         for (uint32_t q = 0; q < Q; ++q) s_cnt[q * NPAD + d] = 0u;
     } else {
         for (uint32_t v = 0; v < 4 * NW; ++v) s_hm[v * NPAD + d] = 0ull;
+    }
+    if constexpr (PAT) {
+        ((uint32_t*)s_oA)[d] = 0u;                   // oA and oB: 4 NPAD bytes
+        if (d < 8) s_pcnt[d] = 0u;
+        if (lane == 0) s_pbyz[wid] = byzw;
     }
     __syncthreads();
     {
@@ -102,9 +128,25 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
             if (cF) atomicAdd(&s_ctl[1], cF);
             if (cS) atomicAdd(&s_ctl[2], cS);
         }
+        if constexpr (PAT) {
+            // ... and per parity (64 is even: lane parity = replica parity), with the Byzantine replicas' count
+            const uint64_t bF = __ballot(honest && laneF), bS = __ballot(honest && !laneF), ev = 0x5555555555555555ull;
+            const uint32_t c4[5] = {(uint32_t)__popcll(bF & ev), (uint32_t)__popcll(bF & ~ev), (uint32_t)__popcll(bS & ev),
+                                    (uint32_t)__popcll(bS & ~ev), (uint32_t)__popcll(__ballot(real && !honest))};
+            if (lane == 0) {
+#pragma unroll
+                for (int q = 0; q < 5; ++q) if (c4[q]) atomicAdd(&s_pcnt[q], c4[q]);
+            }
+        }
     }
     __syncthreads();
     const uint32_t nHF = uni32(s_ctl[1]), nHS = uni32(s_ctl[2]);
+    uint32_t nFe = 0, nFo = 0, nSe = 0, nSo = 0;
+    bool any_byz = false;                            // block-uniform
+    if constexpr (PAT) {
+        nFe = uni32(s_pcnt[0]); nFo = uni32(s_pcnt[1]); nSe = uni32(s_pcnt[2]); nSo = uni32(s_pcnt[3]);
+        any_byz = uni32(s_pcnt[4]) != 0;
+    }
 
     // ---- block reduction: OR of x over the workgroup (rotating LDS slots, one barrier; brc_step_wide.h block_red)
     uint32_t rctr = 0;
@@ -371,8 +413,120 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
         send_key(0, v & 3);
         if constexpr (SPEC) spec_advance();
     }
-    if (block_or(ovf ? 1u : 0u)) status = BRC_OVERFLOW;
-    else simulate_new();
+    if (block_or(ovf ? 1u : 0u)) {
+        status = BRC_OVERFLOW;
+    } else {
+        simulate_new();
+        if constexpr (PAT) {
+            // ---- the equivocation pattern: every Byzantine lane's two keys (b NV + v, s = 0), value id 1 + v.
+            // simulate_batch over four receiver classes: [0] fast in [1] fast out [2] slow in [3] slow out ("in": the
+            // replica's parity is v, it gets the SEND); nC their honest sizes.  The origin is this lane (t = 0).
+            auto simulate_pattern = [&](const bool has, const uint32_t v) {
+                const uint32_t nC[4] = {v ? nFo : nFe, v ? nFe : nFo, v ? nSo : nSe, v ? nSe : nSo};
+                const uint32_t k = (d * NV + v) * Q, x = 2 * d + v;
+                const bool oF = laneF;
+                // bit j of field S (bits 0-9), E (10-19), R (20-29) <=> something may land at step r + j (a superset:
+                // the arrivals below are exact).  The SEND lands at 1 (fast origin, fast class) or Dd; the origin's
+                // ECHO and READY, stamped 1, at 2 or 1 + Dd
+                uint32_t pend = 0;
+                if (has) {
+                    s_meta[k] = (1u << 16) | ((1u + v) << 14) | 1u;
+                    st_msgs += v ? n / 2u : (n + 1u) / 2u;          // the SEND, to every replica of parity v
+                    pend = (1u << (Dd - 1u)) | (1u << (10u + Dd)) | (1u << (20u + Dd));
+                    if (oF) pend |= 1u | (1u << 11) | (1u << 21);
+                }
+                {
+                    // the origin's ECHO and READY of this key go to all n replicas at step 1
+                    const uint32_t c = (uint32_t)__popcll(__ballot(has));
+                    if (lane == 0 && c) atomicAdd(&s_rg[RW + 1], 2u * n * c);
+                }
+                uint32_t fl[4] = {0, 0, 0, 0}, ec[4] = {0, 0, 0, 0}, rc[4] = {0, 0, 0, 0};
+                uint32_t sE = 0xFFFFFFFFu, sR = 0xFFFFFFFFu;        // byte c: the step class c SENT ECHO / READY (0xFF: not)
+                uint32_t last = 1;
+                uint32_t rstep = 1;
+                auto wsum = [&](uint32_t y) -> uint32_t {
+#pragma unroll
+                    for (int o = 32; o; o >>= 1) y += (uint32_t)__shfl_xor((int)y, o);
+                    return y;
+                };
+#pragma unroll 1
+                for (uint32_t r = 1; ; r += rstep) {
+                    if (!__ballot(pend != 0u)) break;
+                    bool due = (pend & (1u | (1u << 10) | (1u << 20))) != 0;
+                    if (due && r > RW) {                             // past the ring (cannot happen for Dd <= 8)
+                        ovf = true; due = false;
+                        pend = 0;
+                    }
+                    const uint32_t row = r & (RW - 1);
+                    const uint32_t c1 = r - 1u, cD = r >= Dd ? r - Dd : 0x100u;
+                    // ECHO / READY arrivals at a fast (F) and at a slow (S) receiver: fast senders land on fast
+                    // receivers after 1 step, every other pair after Dd; the origin's own count one each
+                    uint32_t eF = 0, eS = 0, rF = 0, rS = 0;
+#pragma unroll
+                    for (uint32_t c = 0; c < 4; ++c) {
+                        const uint32_t xe = (sE >> (8 * c)) & 0xFFu, xr = (sR >> (8 * c)) & 0xFFu;
+                        const uint32_t eD = xe == cD ? nC[c] : 0u, rD = xr == cD ? nC[c] : 0u;
+                        eS += eD; rS += rD;
+                        if (c < 2) { eF += xe == c1 ? nC[c] : 0u; rF += xr == c1 ? nC[c] : 0u; }
+                        else { eF += eD; rF += rD; }
+                    }
+                    const uint32_t oS = r == 1u + Dd ? 1u : 0u, oFst = r == (oF ? 2u : 1u + Dd) ? 1u : 0u;
+                    eF += oFst; rF += oFst; eS += oS; rS += oS;
+                    const uint32_t sa[4] = {r == (oF ? 1u : Dd) ? 1u : 0u, 0u, r == Dd ? 1u : 0u, 0u};
+                    const bool hS = due && (sa[0] | sa[2]) != 0, hE = due && (eF | eS) != 0, hR = due && (rF | rS) != 0;
+                    uint32_t arr = 0, msgs = 0, cells = 0, dels = 0, esm = 0, rsm = 0;
+#pragma unroll
+                    for (uint32_t c = 0; c < 4; ++c) {
+                        const uint32_t e = c < 2 ? eF : eS, q = c < 2 ? rF : rS;
+                        const uint32_t a = due ? e + q + sa[c] : 0u;
+                        const bool opn = nC[c] != 0 && a != 0 && !(fl[c] & F_DEL);   // a delivered cell ignores everything
+                        uint32_t es = 0, rs = 0, dl = 0, nr = 0;
+                        if (due) upd_cell(fl[c], ec[c], rc[c], opn, sa[c], e, q, hS, hE, hR, es, rs, dl, nr);
+                        arr += nC[c] * a;
+                        msgs += nC[c] * (es + rs);
+                        cells += a ? nC[c] : 0u;
+                        dels += dl ? nC[c] : 0u;
+                        if (es) esm |= 0xFFu << (8 * c);
+                        if (rs) rsm |= 0xFFu << (8 * c);
+                        if (dl) {
+                            // class c delivers the key at step r, whole (this lane's own slot and table entry)
+                            const uint8_t tc = (uint8_t)(0x80u | (r & 0x7Fu));
+                            if (c == 0) s_dA[k] = tc;
+                            else if (c == 1) s_oA[x] = tc;
+                            else if (c == 2) s_dB[k] = tc;
+                            else s_oB[x] = tc;
+                        }
+                    }
+                    sE = (sE & ~esm) | ((r * 0x01010101u) & esm);
+                    sR = (sR & ~rsm) | ((r * 0x01010101u) & rsm);
+                    // step statistics over the wave's batch: whole words, one atomic per counter; the row is marked
+                    // only when a message reaches an honest receiver
+                    if (__ballot(due)) {
+                        const uint32_t wa = wsum(arr), wm = wsum(msgs), wc = wsum(cells), wd = wsum(dels);
+                        if (lane == 0) {
+                            if (wa) { atomicAdd(&s_rg[row], wa); atomicOr(&s_ctl[0], 1u << row); }
+                            if (wm) atomicAdd(&s_rg[RW + row], n * wm);
+                            if (wc) atomicAdd(&s_rg[2 * RW + row], wc);
+                            if (wd) atomicAdd(&s_rg[3 * RW + row], wd);
+                            st_ksteps += (uint32_t)__popcll(__ballot(due));
+                        }
+                    }
+                    // what the classes sent now may land on the fast classes after 1 step, anywhere after Dd
+                    if (esm) pend |= ((esm & 0xFFFFu) ? 1u << 11 : 0u) | (1u << (10u + Dd));
+                    if (rsm) pend |= ((rsm & 0xFFFFu) ? 1u << 21 : 0u) | (1u << (20u + Dd));
+                    if (arr) last = r;
+                    pend &= ~(1u | (1u << 10) | (1u << 20));
+                    const uint32_t m = uni32(wave_or_all((pend | (pend >> 10) | (pend >> 20)) & 0x3FFu));
+                    rstep = m ? (uint32_t)__builtin_ctz(m) : 1u;
+                    pend >>= rstep;
+                }
+                if (has) s_meta[k] = (s_meta[k] & 0xFFFFu) | (last << 16);
+            };
+            const bool byz_lane = real && !honest;
+            simulate_pattern(byz_lane, 0u);
+            simulate_pattern(byz_lane, 1u);
+        }
+    }
     __syncthreads();                                 // the new keys' ring rows, class bytes and slot stamps
 
     const uint64_t gm0 = (1ull << Q) - 1;            // Q <= 32
@@ -380,7 +534,10 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
         // next step with arrivals at an honest receiver (every thread reads the same word, after a barrier)
         const uint32_t rows = uni32(s_ctl[0]);
         const uint32_t rot = (t + 1) & (RW - 1);
-        const uint32_t rr = rot ? ((rows >> rot) | (rows << (RW - rot))) : rows;
+        uint32_t rr = rot ? ((rows >> rot) | (rows << (RW - rot))) : rows;
+        if constexpr (PAT) {
+            if (t == 0 && any_byz) rr |= 1u;         // step 1: the pattern's ECHOs and READYs are sent then
+        }
         if (!rr) { status = BRC_QUIESCENT; break; }
         const uint32_t next = t + 1 + (uint32_t)__builtin_ctz(rr);
         if (next > P.step_cap) { status = BRC_STEPCAP; break; }
@@ -392,6 +549,9 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
             const uint32_t ce = uni32(s_rg[2 * RW + row]), de = uni32(s_rg[3 * RW + row]);
             if (tid == 0) { st_arr += a; st_msgs += mg; st_cells += ce; st_del += de; }
             if (ce) t_stop = t;
+            if constexpr (PAT) {
+                if (t == 1 && any_byz) t_stop = t;   // an action step counts as active
+            }
         }
         // the step's two class bitmaps per key word: the keys whose delivery step for the class is now; consumed
         // entries are freed for step t + 128 here, by the wave that ballots the word
@@ -400,8 +560,26 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
             for (uint32_t w = wid; w < nkw; w += NW) {
                 const uint32_t kk = w * 64 + lane;
                 const bool a = s_dA[kk] == tc, b = s_dB[kk] == tc;
-                const uint64_t kA = __ballot(a), kB = __ballot(b);
-                if (lane == 0) { s_kab[2 * w] = kA; s_kab[2 * w + 1] = kB; }
+                if constexpr (PAT) {
+                    // a pattern key (phase slot 0 of variant v = 0 / 1 of a Byzantine origin): dA / dB hold its
+                    // in-classes (replica parity v), oA / oB the out-classes; any other key: both parities alike
+                    const uint32_t o = kk >> ksh, v = (kk >> qsh) & (NV - 1u);
+                    const bool pat = (kk & Qm) == 0 && v < 2 && ((s_pbyz[o >> 6] >> (o & 63)) & 1ull);
+                    bool ao = a, bo = b;
+                    if (pat) {
+                        const uint32_t x = 2 * o + v;
+                        ao = s_oA[x] == tc; bo = s_oB[x] == tc;
+                        if (ao) s_oA[x] = 0;
+                        if (bo) s_oB[x] = 0;
+                    }
+                    const bool odd = pat && v == 1;  // in-class parity
+                    const uint64_t kAe = __ballot(odd ? ao : a), kBe = __ballot(odd ? bo : b);
+                    const uint64_t kAo = __ballot((pat && !odd) ? ao : a), kBo = __ballot((pat && !odd) ? bo : b);
+                    if (lane == 0) { s_kab[4 * w] = kAe; s_kab[4 * w + 1] = kBe; s_kab[4 * w + 2] = kAo; s_kab[4 * w + 3] = kBo; }
+                } else {
+                    const uint64_t kA = __ballot(a), kB = __ballot(b);
+                    if (lane == 0) { s_kab[2 * w] = kA; s_kab[2 * w + 1] = kB; }
+                }
                 if (a) s_dA[kk] = 0;
                 if (b) s_dB[kk] = 0;
             }
@@ -416,10 +594,10 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
         // ================= consensus: this step's deliveries in canonical (kp, s) order, each replica its own
         defer = true;
         if (cons_lane) {
-            const uint32_t cls = laneF ? 0u : 1u;
+            const uint32_t cls = (laneF ? 0u : 1u) + (PAT ? 2u * (d & 1u) : 0u);
 #pragma unroll 1
             for (uint32_t w = 0; w < nkw; ++w) {
-                uint64_t bits = s_kab[2 * w + cls];
+                uint64_t bits = s_kab[KC * w + cls];
                 // one delivery at a time, ascending slot; several phases of one key prefix: smallest s first
                 while (bits) {
                     uint32_t best = (uint32_t)__ffsll((unsigned long long)bits) - 1u;
@@ -486,9 +664,9 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
     }
 }
 
-template <int NPAD, int MODE>
+template <int NPAD, int MODE, bool PAT = false>
 int launch_life_wide_one(uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P) {
-    auto kern = brc_life_wide<NPAD, MODE>;
+    auto kern = brc_life_wide<NPAD, MODE, PAT>;
     if (lds > 64 * 1024 &&
         hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return BRC_E_HIP;
@@ -501,6 +679,14 @@ int launch_life_wide_npad(int mode, uint32_t blocks, uint32_t lds, hipStream_t s
     if (mode == BRC_MODE_SPEC) return launch_life_wide_one<NPAD, BRC_MODE_SPEC>(blocks, lds, s, P);
     if (mode == BRC_MODE_BEB) return launch_life_wide_one<NPAD, BRC_MODE_BEB>(blocks, lds, s, P);
     if (mode == BRC_MODE_REFERENCE) return launch_life_wide_one<NPAD, BRC_MODE_REFERENCE>(blocks, lds, s, P);
+    return BRC_E_INVALID;
+}
+
+// the pattern form (BRC_FLAG_LIFE_PATTERN): REFERENCE / BEB
+template <int NPAD>
+int launch_life_wide_pat_npad(int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P) {
+    if (mode == BRC_MODE_BEB) return launch_life_wide_one<NPAD, BRC_MODE_BEB, true>(blocks, lds, s, P);
+    if (mode == BRC_MODE_REFERENCE) return launch_life_wide_one<NPAD, BRC_MODE_REFERENCE, true>(blocks, lds, s, P);
     return BRC_E_INVALID;
 }
 

@@ -30,6 +30,8 @@ Workloads:
              instances per GPU (informational: no earlier build runs it)
   cfg5-const-life, cfg5-ref-slow-life, cfg5-ref-slow-q16-life  their step rows' dictionaries plus BRC_FLAG_WIDE_LIFE (the
              wide key-lifetime kernel); cfg5-ref-slow-q16-life-6144: the q16 run at 6144 instances (informational)
+  cfg5-ref-slow-eq[-life]  cfg5-ref-slow's committee with replicas 171..255 equivocating (BRC_BYZ_EQUIVOCATE, key window 4,
+             two variants) on the wide step kernel; -life: plus BRC_FLAG_WIDE_LIFE | BRC_FLAG_LIFE_PATTERN (informational)
 
 A step is one pass of the hot path over the batch (reset + run to completion); the timed region
 is K steps between barriers, max over ranks.  `roofline.achieved` = this layout's algorithmic
@@ -133,6 +135,12 @@ def workloads(L):
     # ... and the q16 run at cfg5's batch: 8 MB of cells per instance cap the step kernel at 384 instances, the
     # lifetime kernel allocates none
     W["cfg5-ref-slow-q16-life-6144"] = (6144, True, dict(W["cfg5-ref-slow-q16-life"][2]))
+    # cfg5-ref-slow's committee with replicas 171..255 Byzantine and equivocating (BRC_BYZ_EQUIVOCATE, two key variants):
+    # on the wide step kernel, and the same dictionary on the wide key-lifetime kernel's pattern form
+    # (BRC_FLAG_LIFE_PATTERN; informational: a pair counts the same cell-steps)
+    W["cfg5-ref-slow-eq"] = (6144, True, dict(W["cfg5-ref-slow"][2], key_window=4, variants=2,
+                                              byz_pattern=L.BYZ_EQUIVOCATE, byzantine=list(range(171, 256))))
+    W["cfg5-ref-slow-eq-life"] = (6144, True, dict(W["cfg5-ref-slow-eq"][2], wide_life=True, life_pattern=True))
     return W
 
 

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define BRC_ABI_VERSION 11
+#define BRC_ABI_VERSION 12
 
 enum {
     BRC_OK = 0,
@@ -165,9 +165,26 @@ typedef struct {
  * connection peers, the broadcast protocol, no proposals, uniform / geometric delays, delay_max > 8, an event log, a
  * pattern, BRC_FLAG_WIDE_RECORDS / BRC_FLAG_WIDE_VALUES (they select the step kernel's record / 3-bit forms), an LDS
  * carve above 160 KB, and BRC_KERNEL=step in the environment (a lifetime-only engine has no step state).  Without
- * the flag nothing changes: BRC_KERNEL=life at n > 64 still runs the step kernel. */
+ * the flag nothing changes: BRC_KERNEL=life at n > 64 still runs the step kernel.
+ * BRC_FLAG_LIFE_PATTERN (v12): together with BRC_FLAG_WIDE_LIFE, byz_pattern = BRC_BYZ_EQUIVOCATE runs on the wide
+ * key-lifetime kernel (its pattern form, csrc/brc_life_wide.h PAT).  The pattern is a function of the instance's
+ * Byzantine mask: Byzantine replica b declares the keys (b * variants + v, s = 0) with value id 1 + v (v = 0, 1), SENDs
+ * key 0 to the even replicas and key 1 to the odd ones at t = 0, and ECHOes and READYs both to everyone at t = 1.  The
+ * kernel reads the mask itself and simulates such a key as four receiver-class states ((fast | slow) x (got the SEND |
+ * did not)), so the engine keeps no injection list for the pattern; brc_load_byzantine (per-instance masks),
+ * brc_reset, brc_reset_at, brc_load_proposals and every reader work, and the engine is lifetime-only like any
+ * BRC_FLAG_WIDE_LIFE engine (brc_inject and stepped runs: BRC_E_UNSUPPORTED).  Results are those of an unflagged
+ * engine running the pattern on the wide step kernel, field for field.  Eligible: everything BRC_FLAG_WIDE_LIFE
+ * requires, BRC_MODE_REFERENCE or BRC_MODE_BEB, variants 2 or 4 (key_window * variants <= 8, or 16 / 32 with
+ * BRC_FLAG_WIDE_WINDOWS).  One workgroup's LDS is BRC_FLAG_WIDE_LIFE's plus 16 B per 64 key slots and 64 B + 4 NPAD:
+ * 16 / 23 / 37 KB at NPAD 128 and 48 / 62 / 90 KB at NPAD 256 for key_window * variants = 8 / 16 / 32 with variants = 2
+ * (16,512 .. 91,776 B; a carve above 160 KB would be refused as under BRC_FLAG_WIDE_LIFE).  The flag set
+ * on anything else fails brc_create with BRC_E_INVALID and a reason naming it: without BRC_FLAG_WIDE_LIFE, n <= 64 (a
+ * pattern there runs on the step kernel, as it does at n in 33..64 whatever the flags), connection peers,
+ * BRC_MODE_SPEC (variants = 1 above 64 replicas), byz_pattern = BRC_BYZ_NONE, variants = 1.  Without the flag nothing
+ * changes: BRC_FLAG_WIDE_LIFE with a pattern is still refused. */
 enum { BRC_FLAG_GENERAL_KEYS = 1, BRC_FLAG_WIDE_RECORDS = 2, BRC_FLAG_WIDE_VALUES = 4, BRC_FLAG_WIDE_WINDOWS = 8,
-       BRC_FLAG_WIDE_LIFE = 16 };
+       BRC_FLAG_WIDE_LIFE = 16, BRC_FLAG_LIFE_PATTERN = 32 };
 
 /* Injections may arrive between brc_run calls.  A record's time must not lie before the step its instance's wave
  * item stands at (brc_instance_result.t_now once the engine has run): t < t_now is BRC_E_STATE.  t == t_now is
