@@ -21,6 +21,7 @@
 #include <unordered_map>
 
 #include "brc_internal.h"
+#include "brc_plan.h"
 
 namespace {
 
@@ -141,21 +142,9 @@ template <typename W> __global__ void fill_words(W* p, W v, uint64_t count) {
 }
 
 // ------------------------------------------------------------------------------------ host
-struct Engine {
+// The plan (brc_plan.h: geometry, kernel family, buffer sizes -- fixed by brc_create) and the engine's run-time state
+struct Engine : Plan {
     brc_config cfg;
-    int npad = 0, dm = 0, ipw = 0, nkw_t = 0;
-    bool wide = false;                           // n > 64: one workgroup per instance (brc_step_wide.h)
-    bool wide_wv4 = false;                       // wide: the 4-waves-per-SIMD instantiations (brc_step_wide.h WV)
-    bool regmask = false;                        // NPAD = 64 lean kernel with register delay masks (NLR = 2)
-    bool compact = false;                        // lean kernels (NPAD = 64, sender peers): u32 cells (C32_*)
-    bool general = false;                        // BRC_FLAG_GENERAL_KEYS at NPAD = 64 (KMODE_XREF)
-    uint32_t lpi = 64;                           // replica lanes per item (64, or NPAD when wide)
-    uint32_t bw = 1;                             // Byzantine-mask words per instance
-    uint32_t NK = 0, nkw = 0, msize = 0, lds_bytes = 0;
-    uint32_t rows = 0;                           // cell rows per item
-    uint32_t rs = TS;                            // activity-ring rows: ring_steps(dm)
-    uint64_t cons_bytes = 0;                     // consensus-set buffer (hmask) bytes per item
-    uint64_t nitems = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_ms = 0.f;
@@ -171,11 +160,8 @@ struct Engine {
     unsigned long long* gcount = nullptr;
     uint64_t* dbits = nullptr;                   // lean SPEC: per-wave delivery bitmaps (brc_step.h DBG)
     uint64_t* dring = nullptr;                   // per-link lifetime kernel: delivery bitmap ring (brc_life.h)
-    uint32_t* lmeta = nullptr;                   // lifetime kernel, key windows >= 64: slot metadata in HBM
+    uint32_t* lmeta = nullptr;                   // two-class lifetime kernel, key windows >= 32 (life_hbm_meta): slot metadata in HBM
     uint64_t* xsend = nullptr; uint32_t* xsn = nullptr;   // extra-SEND records (non-lean step kernels)
-    bool life_pl = false;                        // lifetime kernel in its per-link delay form
-    uint32_t life_rw = LIFE_RW;                  // ... its delivery-ring rows (LIFE_RW16 for delays above 8)
-    uint32_t nval = 4;                           // consensus value ids the step kernel keeps (value_ids)
     bool values_wide = false;                    // a loaded proposal uses a value id >= 4 (no lifetime kernel)
     Params* dparams = nullptr;                   // device copy of the launch parameters
     Params hparams;
@@ -208,22 +194,16 @@ struct Engine {
     std::unordered_map<uint64_t, bool> msg_rec;
     // the same on the wide kernels under BRC_FLAG_WIDE_RECORDS (brc_step_wide.h REC): one instance per item, one
     // sender per record, destination and used-link sets of bw words (four kept).  type 0: an extra SEND
-    bool wide_rec = false;
-    bool wide_val = false;                       // BRC_FLAG_WIDE_VALUES: the wide kernels with 3-bit value ids (V8)
     struct WRec { uint32_t k, t, type, node; uint64_t dst[4]; };
     struct WUsed { uint64_t w[4] = {0, 0, 0, 0}; bool rec = false; };
     std::unordered_map<uint64_t, std::vector<WRec>> wrec;   // instance -> records in flight (P.xsend)
     std::map<std::pair<uint64_t, uint64_t>, WUsed> wmsg;    // (instance, wmsg_key) -> links used, had a record
     std::vector<uint64_t> hbyz;                 // host copy of the per-instance Byzantine masks [instance][bw]
-    // key-lifetime kernel (brc_life.h): eligible configuration, engine fresh since create / reset,
+    // key-lifetime kernel (brc_life.h; life_cfg: eligible configuration): engine fresh since create / reset,
     // and whether the last run used it (its instances are then final: no re-opening injections)
-    bool life_cfg = false, fresh = true, life_done = false, last_life = false;
-    // false: the step kernel cannot serve this engine (its cells would not fit, or a lean key window
-    // above 32): only the key-lifetime kernel runs, and the step kernel's key-slot arrays are not allocated
-    bool step_ok = true;
+    bool fresh = true, life_done = false, last_life = false;
     bool cells_ready = false;                    // the step kernel's cell array (allocated on first use
                                                  // when the lifetime kernel may serve the engine)
-    uint32_t life_lds = 0;
 };
 
 thread_local std::string g_create_err;    // brc_last_error(NULL): the last brc_create failure
@@ -236,12 +216,6 @@ thread_local std::string g_create_err;    // brc_last_error(NULL): the last brc_
             return BRC_E_HIP;                                                          \
         }                                                                              \
     } while (0)
-
-static int pick_npad(uint32_t n) {
-    int p = 4;
-    while ((uint32_t)p < n) p *= 2;
-    return p;
-}
 
 // bits of replicas 64w .. 64w+63 that exist in an n-replica instance
 static uint64_t word_mask(uint32_t n, uint32_t w) {
@@ -259,8 +233,6 @@ static uint64_t wmsg_key(uint32_t node, uint32_t type, uint32_t kp, uint32_t s) 
     return ((uint64_t)node << 40) | ((uint64_t)(type == BRC_READY) << 32) | ((uint64_t)kp << 16) | s;
 }
 
-static int pick_dm(uint32_t d) { return d <= 4 ? 4 : d <= 8 ? 8 : 16; }
-
 // Slot generations (tagged kernels): how far this epoch can have advanced the tag of one key slot, plus one to
 // spare.  The kernels allocate a slot (gen + 1, brc_step.h) in send_key_now -- a replica's own key of phase index
 // s, once per s and pass, s rising within a pass (a PROPOSE starts the next pass) -- and in send_rec, for every
@@ -273,31 +245,37 @@ static uint64_t gen_used(const Engine* e) {
     return gen_passes(e) * (e->gen_smax / e->cfg.key_window + 1) + e->gen_extra + 1;
 }
 
-static int launch_step(int npad, int dm, bool events, int mode, bool wv4, bool rec, bool v8, uint32_t blocks, uint32_t lds,
-                       hipStream_t st, const Params* P) {
-    if (v8) return npad == 128 ? launch_step_128v(dm, events, mode, blocks, lds, st, P)
-                               : launch_step_256v(dm, events, mode, blocks, lds, st, P);
-    if (rec) return npad == 128 ? launch_step_128x(dm, events, mode, blocks, lds, st, P)
-                                : launch_step_256x(dm, events, mode, blocks, lds, st, P);
+// The one place a kernel is chosen: the plan's family and this run's `life` decision (brc_run)
+static int launch_kernel(const Engine* e, bool life, const Params* P) {
+    const int npad = e->npad, dm = e->dm, mode = e->kmode;
+    const bool events = e->cfg.event_capacity != 0;
+    const uint32_t items = (uint32_t)e->nitems, lds = e->lds_bytes;
+    const uint32_t blocks = e->wide ? items : (uint32_t)((e->nitems + WPB - 1) / WPB);
+    hipStream_t st = e->stream;
+    if (life && e->wide) {
+        // the wide key-lifetime kernel (BRC_FLAG_WIDE_LIFE): one workgroup of NPAD threads per instance
+        if (e->life_pat) return npad == 128 ? launch_life_128p(mode, items, e->life_lds, st, P)
+                              : npad == 256 ? launch_life_256p(mode, items, e->life_lds, st, P) : BRC_E_INVALID;
+        return npad == 128 ? launch_life_128(mode, items, e->life_lds, st, P)
+             : npad == 256 ? launch_life_256(mode, items, e->life_lds, st, P) : BRC_E_INVALID;
+    }
+    if (life) return launch_life(mode, e->life_pl, e->life_rw == LIFE_RW16, e->cfg.key_window >= 64, e->has_lmeta, items,
+                                 e->life_lds, st, P);
+    if (e->regmask) return launch_step_64r(dm, events, mode, blocks, lds, st, P);
+    if (e->wide_val) return npad == 128 ? launch_step_128v(dm, events, mode, blocks, lds, st, P)
+                                        : launch_step_256v(dm, events, mode, blocks, lds, st, P);
+    if (e->wide_rec) return npad == 128 ? launch_step_128x(dm, events, mode, blocks, lds, st, P)
+                                        : launch_step_256x(dm, events, mode, blocks, lds, st, P);
     switch (npad) {
     case 4: return launch_step_4(dm, events, mode, blocks, lds, st, P);
     case 8: return launch_step_8(dm, events, mode, blocks, lds, st, P);
     case 16: return launch_step_16(dm, events, mode, blocks, lds, st, P);
     case 32: return launch_step_32(dm, events, mode, blocks, lds, st, P);
     case 64: return launch_step_64(dm, events, mode, blocks, lds, st, P);
-    case 128: return launch_step_128(dm, events, mode, wv4, blocks, lds, st, P);
-    case 256: return launch_step_256(dm, events, mode, wv4, blocks, lds, st, P);
+    case 128: return launch_step_128(dm, events, mode, e->wide_wv4, blocks, lds, st, P);
+    case 256: return launch_step_256(dm, events, mode, e->wide_wv4, blocks, lds, st, P);
     default: return BRC_E_INVALID;
     }
-}
-
-// the wide key-lifetime kernel (BRC_FLAG_WIDE_LIFE): one workgroup of NPAD threads per instance
-// pat: its pattern form (BRC_FLAG_LIFE_PATTERN)
-static int launch_life_wide(int npad, int mode, bool pat, uint32_t blocks, uint32_t lds, hipStream_t st, const Params* P) {
-    if (pat) return npad == 128 ? launch_life_128p(mode, blocks, lds, st, P)
-                  : npad == 256 ? launch_life_256p(mode, blocks, lds, st, P) : BRC_E_INVALID;
-    return npad == 128 ? launch_life_128(mode, blocks, lds, st, P)
-         : npad == 256 ? launch_life_256(mode, blocks, lds, st, P) : BRC_E_INVALID;
 }
 
 static void free_all(Engine* e) {
@@ -311,7 +289,7 @@ static void free_all(Engine* e) {
 }
 
 static int fill_cells(Engine* e) {
-    const size_t cells = (size_t)e->nitems * e->rows * e->lpi;
+    const uint64_t cells = e->cells_n;
     const uint64_t fb = std::min<uint64_t>((cells + 255) / 256, 1u << 20);
     if (e->compact)
         hipLaunchKernelGGL(fill_words<uint32_t>, dim3((uint32_t)fb), dim3(256), 0, e->stream, (uint32_t*)e->cells,
@@ -326,7 +304,7 @@ static int fill_cells(Engine* e) {
 // the step kernel's cells, allocated at its first launch on an engine the lifetime kernel may serve
 static int ensure_cells(Engine* e) {
     if (e->cells_ready) return BRC_OK;
-    const size_t bytes = (size_t)e->nitems * e->rows * e->lpi * (e->compact ? 4 : 8);
+    const size_t bytes = e->cells_bytes;
     if (e->cells) (void)hipFree(e->cells);
     e->cells = nullptr;
     if (hipMalloc(&e->cells, std::max<size_t>(bytes, 8)) != hipSuccess) {
@@ -339,7 +317,6 @@ static int ensure_cells(Engine* e) {
 }
 
 static int clear_state(Engine* e, bool full) {
-    const size_t keys = (size_t)e->cfg.instances * e->NK;
     if (!e->step_ok) {
         // lifetime kernel only: it keeps key slots in LDS; no cells, key metadata or activity ring
     } else if (full) {
@@ -347,26 +324,25 @@ static int clear_state(Engine* e, bool full) {
             const int rc = fill_cells(e);
             if (rc) return rc;
         }
-        HIPCHK(e, hipMemsetAsync(e->meta, 0, keys * 8, e->stream));
-        HIPCHK(e, hipMemsetAsync(e->mgen, 0, keys * 4, e->stream));
+        HIPCHK(e, hipMemsetAsync(e->meta, 0, e->meta_bytes, e->stream));
+        HIPCHK(e, hipMemsetAsync(e->mgen, 0, e->mgen_bytes, e->stream));
         e->gen_base = 0;
         e->gen_cur = 0;
     } else {
-        hipLaunchKernelGGL(reset_slots, dim3((uint32_t)((keys + 255) / 256)), dim3(256), 0, e->stream, e->meta, e->mgen,
-                           (uint64_t)keys);
+        hipLaunchKernelGGL(reset_slots, dim3((uint32_t)((e->keys + 255) / 256)), dim3(256), 0, e->stream, e->meta, e->mgen,
+                           e->keys);
         HIPCHK(e, hipGetLastError());
     }
-    if (e->step_ok)
-        HIPCHK(e, hipMemsetAsync(e->act, 0, (size_t)e->nitems * e->rs * e->nkw * act_types(e->compact, e->ipw) * 8, e->stream));
-    HIPCHK(e, hipMemsetAsync(e->actany, 0, (size_t)e->nitems * 4, e->stream));
-    HIPCHK(e, hipMemsetAsync(e->items, 0, (size_t)e->nitems * sizeof(ItemState), e->stream));
-    HIPCHK(e, hipMemsetAsync(e->inst, 0, (size_t)e->cfg.instances * sizeof(InstState), e->stream));
-    HIPCHK(e, hipMemsetAsync(e->istats, 0, (size_t)e->cfg.instances * 4 * 8, e->stream));
-    HIPCHK(e, hipMemsetAsync(e->cons0, 0, (size_t)e->nitems * e->lpi * 8, e->stream));
-    HIPCHK(e, hipMemsetAsync(e->cons1, 0, (size_t)e->nitems * e->lpi * 8, e->stream));
-    if (e->cons_bytes) HIPCHK(e, hipMemsetAsync(e->hmask, 0, (size_t)e->nitems * e->cons_bytes, e->stream));
+    if (e->step_ok) HIPCHK(e, hipMemsetAsync(e->act, 0, e->act_bytes, e->stream));
+    HIPCHK(e, hipMemsetAsync(e->actany, 0, e->item_u32_bytes, e->stream));
+    HIPCHK(e, hipMemsetAsync(e->items, 0, e->items_bytes, e->stream));
+    HIPCHK(e, hipMemsetAsync(e->inst, 0, e->inst_bytes, e->stream));
+    HIPCHK(e, hipMemsetAsync(e->istats, 0, e->istats_bytes, e->stream));
+    HIPCHK(e, hipMemsetAsync(e->cons0, 0, e->cons_rec_bytes, e->stream));
+    HIPCHK(e, hipMemsetAsync(e->cons1, 0, e->cons_rec_bytes, e->stream));
+    if (e->cons_bytes) HIPCHK(e, hipMemsetAsync(e->hmask, 0, e->hmask_bytes, e->stream));
     HIPCHK(e, hipMemsetAsync(e->gcount, 0, 8 * 8, e->stream));
-    if ((!e->compact && !e->wide) || e->wide_rec) HIPCHK(e, hipMemsetAsync(e->xsn, 0, (size_t)e->nitems * 4, e->stream));
+    if (e->has_xsn) HIPCHK(e, hipMemsetAsync(e->xsn, 0, e->xsn_bytes, e->stream));
     if (e->event_count) HIPCHK(e, hipMemsetAsync(e->event_count, 0, 8, e->stream));
     return BRC_OK;
 }
@@ -450,217 +426,21 @@ int brc_create(const brc_config* cfg, void** out) {
     if (!cfg || !out) { g_create_err = "null argument"; return BRC_E_INVALID; }
     *out = nullptr;
     const brc_config& c = *cfg;
-    if (c.flags & BRC_FLAG_LIFE_PATTERN) {
-        // the equivocation pattern on the wide key-lifetime kernel (brc_life_wide.h PAT): what the flag needs besides
-        // BRC_FLAG_WIDE_LIFE's own conditions (below).  First, so that each of these gets its reason
-        const char* why =
-            !(c.flags & BRC_FLAG_WIDE_LIFE) ? "BRC_FLAG_LIFE_PATTERN needs BRC_FLAG_WIDE_LIFE (flags): it selects the wide "
-                                              "key-lifetime kernel's pattern form"
-            : c.n <= 64 ? "BRC_FLAG_LIFE_PATTERN is for n > 64: at n <= 64 a byz_pattern runs on the step kernel"
-            : c.peer_mode != BRC_PEER_SENDER ? "BRC_FLAG_LIFE_PATTERN needs sender peers (peer_mode)"
-            : c.mode == BRC_MODE_SPEC ? "BRC_FLAG_LIFE_PATTERN: not with BRC_MODE_SPEC (mode), which has variants = 1 above 64 "
-                                        "replicas and so cannot carry the pattern's two keys per origin"
-            : c.byz_pattern != BRC_BYZ_EQUIVOCATE ? "BRC_FLAG_LIFE_PATTERN needs byz_pattern = BRC_BYZ_EQUIVOCATE: without a "
-                                                    "pattern BRC_FLAG_WIDE_LIFE alone runs the same committee"
-            : (c.variants != 2 && c.variants != 4) ? "BRC_FLAG_LIFE_PATTERN needs variants = 2 or 4: the pattern's keys are "
-                                                     "variants 0 and 1 of a Byzantine origin"
-                                                   : nullptr;
-        if (why) { g_create_err = why; return BRC_E_INVALID; }
-    }
-    if (c.n < 1 || c.n > 256 || c.instances == 0 || c.delay_max < 1 || c.delay_max > 16 ||
-        c.step_cap > STEP_LIMIT || c.peer_mode > BRC_PEER_CONNECTION ||
-        (c.peer_mode == BRC_PEER_CONNECTION && c.mode != BRC_MODE_REFERENCE) ||
-        (c.protocol != BRC_PROTO_BRB && c.protocol != BRC_PROTO_CONSENSUS) || c.delay_model > BRC_DELAY_GEOMETRIC ||
-        (c.delay_model == BRC_DELAY_CONST && (c.delay_const < 1 || c.delay_const > c.delay_max)) ||
-        !(c.key_window == 2 || c.key_window == 4 || c.key_window == 8 || c.key_window == 16 || c.key_window == 32 ||
-          c.key_window == 64 || c.key_window == 128) ||
-        !(c.variants == 1 || c.variants == 2 || c.variants == 4) ||
-        // more than 8 live phase indices per origin: reference / best-effort protocols on the narrow kernels
-        // (up to 128: the reference protocol's many-round runs; the lean kernels take <= 32 and
-        // leave larger windows to the key-lifetime kernel, below)
-        // ... and 16 or 32 on the wide kernels of an engine created with BRC_FLAG_WIDE_WINDOWS (validated below)
-        c.key_window * c.variants > ((c.mode != BRC_MODE_SPEC && c.n <= 64) ? 128u
-                                     : (c.flags & BRC_FLAG_WIDE_WINDOWS)    ? 32u : 8u) ||
-        c.f >= c.n || (c.byz_pattern == BRC_BYZ_EQUIVOCATE && c.variants < 2) ||
-        (c.byz_pattern != BRC_BYZ_NONE && c.byz_pattern != BRC_BYZ_EQUIVOCATE) ||
-        c.proposals > BRC_PROPOSALS_LOADED || c.mode > BRC_MODE_BEB ||
-        (c.flags & ~(uint32_t)(BRC_FLAG_GENERAL_KEYS | BRC_FLAG_WIDE_RECORDS | BRC_FLAG_WIDE_VALUES |
-                               BRC_FLAG_WIDE_WINDOWS | BRC_FLAG_WIDE_LIFE | BRC_FLAG_LIFE_PATTERN)) ||
-        // the general form at NPAD = 64 with sender peers is the reference protocol's (KMODE_XREF)
-        ((c.flags & BRC_FLAG_GENERAL_KEYS) && c.n > 32 && c.n <= 64 && c.peer_mode == BRC_PEER_SENDER &&
-         c.mode != BRC_MODE_REFERENCE) ||
-        (c.n > 64 && c.mode == BRC_MODE_SPEC && c.variants != 1))
-    {
-        g_create_err = "invalid configuration (see include/brc.h field ranges)";
-        return BRC_E_INVALID;
-    }
-    if ((c.flags & BRC_FLAG_WIDE_RECORDS) && (c.n <= 64 || c.peer_mode != BRC_PEER_SENDER)) {
-        g_create_err = c.n <= 64 ? "BRC_FLAG_WIDE_RECORDS is for the wide kernels (n > 64): the narrow kernels take restricted "
-                                   "ECHO / READY records without a flag (n <= 32, or BRC_FLAG_GENERAL_KEYS at n in 33..64)"
-                                 : "BRC_FLAG_WIDE_RECORDS needs sender peers: with connection peers every message is a new "
-                                   "peer, and the records count senders";
-        return BRC_E_INVALID;
-    }
-    if ((c.flags & BRC_FLAG_WIDE_VALUES) && (c.n <= 64 || c.peer_mode != BRC_PEER_SENDER || c.mode == BRC_MODE_SPEC)) {
-        g_create_err = c.n <= 64 ? "BRC_FLAG_WIDE_VALUES is for the wide kernels (n > 64): the narrow kernels keep 3-bit value "
-                                   "ids without it (n <= 32, connection peers, or BRC_FLAG_GENERAL_KEYS at n in 33..64)"
-                     : c.mode == BRC_MODE_SPEC ? "BRC_FLAG_WIDE_VALUES: not with BRC_MODE_SPEC, whose consensus is binary"
-                                               : "BRC_FLAG_WIDE_VALUES needs sender peers: the connection-peer wide kernels "
-                                                 "keep 2-bit value ids";
-        return BRC_E_INVALID;
-    }
-    if ((c.flags & BRC_FLAG_WIDE_WINDOWS) && (c.n <= 64 || c.peer_mode != BRC_PEER_SENDER || c.mode == BRC_MODE_SPEC)) {
-        g_create_err = c.n <= 64 ? "BRC_FLAG_WIDE_WINDOWS is for the wide kernels (n > 64): the narrow kernels take key windows "
-                                   "up to 128 without it"
-                     : c.mode == BRC_MODE_SPEC ? "BRC_FLAG_WIDE_WINDOWS: not with BRC_MODE_SPEC, whose per-phase windows stay <= 8"
-                                               : "BRC_FLAG_WIDE_WINDOWS needs sender peers: the connection-peer wide kernels "
-                                                 "(five words per cell) keep key_window * variants <= 8";
-        return BRC_E_INVALID;
-    }
-    if (c.flags & BRC_FLAG_WIDE_LIFE) {
-        // the wide key-lifetime kernel (brc_life_wide.h): every field it cannot serve is named
-        const char* kv = getenv("BRC_KERNEL");
-        const char* why =
-            c.n <= 64 ? "BRC_FLAG_WIDE_LIFE is for n > 64: at n in 33..64 the key-lifetime kernel runs without a flag"
-            : c.peer_mode != BRC_PEER_SENDER ? "BRC_FLAG_WIDE_LIFE needs sender peers (peer_mode): the wide key-lifetime kernel "
-                                               "has no connection-peer form"
-            : c.protocol != BRC_PROTO_CONSENSUS ? "BRC_FLAG_WIDE_LIFE needs the consensus protocol (protocol): the kernel takes no "
-                                                  "injections, and a broadcast run is made of them"
-            : c.proposals == BRC_PROPOSALS_NONE ? "BRC_FLAG_WIDE_LIFE needs Philox or loaded proposals (proposals)"
-            : (c.delay_model != BRC_DELAY_CONST && c.delay_model != BRC_DELAY_SLOWSET)
-                ? "BRC_FLAG_WIDE_LIFE needs constant or slow-set delays (delay_model): uniform / geometric delays have no "
-                  "two-class form"
-            : c.delay_max > 8 ? "BRC_FLAG_WIDE_LIFE needs delay_max <= 8 (a key's life must fit the 32-step ring)"
-            : c.event_capacity != 0 ? "BRC_FLAG_WIDE_LIFE: no event log (event_capacity): the kernel visits no single message"
-            : (c.byz_pattern != BRC_BYZ_NONE && !(c.flags & BRC_FLAG_LIFE_PATTERN))
-                ? "BRC_FLAG_WIDE_LIFE: no byz_pattern (a pattern is made of injections); silent "
-                  "Byzantine replicas go through byzantine_mask / brc_load_byzantine"
-            : (c.flags & (BRC_FLAG_WIDE_RECORDS | BRC_FLAG_WIDE_VALUES))
-                ? "BRC_FLAG_WIDE_LIFE: not with BRC_FLAG_WIDE_RECORDS / BRC_FLAG_WIDE_VALUES (flags), which select the step "
-                  "kernel's record and 3-bit forms"
-            : (kv && strcmp(kv, "step") == 0) ? "BRC_FLAG_WIDE_LIFE with BRC_KERNEL=step: a lifetime-only engine has no step state"
-                                              : nullptr;
-        if (why) { g_create_err = why; return BRC_E_INVALID; }
-    }
+    PlanEnv env;
+    env.kernel = getenv("BRC_KERNEL");
+    env.total_mem = [](void*, int device, uint64_t* bytes) {
+        if (hipSetDevice(device) != hipSuccess) return false;
+        size_t fr = 0, tot = 0;
+        const bool ok = hipMemGetInfo(&fr, &tot) == hipSuccess;
+        (void)hipGetLastError();
+        *bytes = tot;
+        return ok;
+    };
+    Plan plan;
+    if (make_plan(c, env, &plan, &g_create_err) != BRC_OK) return BRC_E_INVALID;
     Engine* e = new Engine();
+    static_cast<Plan&>(*e) = plan;
     e->cfg = c;
-    e->npad = pick_npad(c.n);
-    e->dm = pick_dm(c.delay_max);
-    e->rs = ring_steps(e->dm);
-    e->wide = e->npad > 64;
-    e->ipw = e->wide ? 1 : 64 / e->npad;
-    e->lpi = e->wide ? (uint32_t)e->npad : 64u;
-    e->bw = e->wide ? (uint32_t)e->npad / 64 : 1u;
-    e->nkw_t = e->npad / 8 < 1 ? 1 : e->npad / 8;
-    // BRC_FLAG_WIDE_WINDOWS: up to 32 key slots per replica lane (NK <= 32 NPAD), as far as the LDS carve allows
-    if (e->npad > 64 && (c.flags & BRC_FLAG_WIDE_WINDOWS)) e->nkw_t = e->npad / 2;
-    e->NK = (uint32_t)e->npad * c.variants * c.key_window;
-    // narrow kernel: + the trash row (brc_step.h); connection peers: 5 words per cell (the cell word
-    // and two 16-step send-count rings, brc_step.h Ring16)
-    const uint32_t cw = c.peer_mode == BRC_PEER_CONNECTION ? 5u : 1u;
-    e->rows = e->wide ? e->NK * cw : (e->NK + 1) * cw;
-    e->nkw = (e->NK + 63) / 64;
-    e->msize = e->npad <= 8 ? 1 : (uint32_t)e->npad / 8;
-    e->nitems = (c.instances + e->ipw - 1) / e->ipw;
-    const bool spec = c.mode == BRC_MODE_SPEC;
-    const uint32_t nL = delay_values(c.delay_model, c.delay_max);
-    // BRC_FLAG_GENERAL_KEYS: NPAD = 64 with sender peers on the general form (KMODE_XREF), not the lean one
-    e->general = (c.flags & BRC_FLAG_GENERAL_KEYS) && e->npad == 64 && c.peer_mode == BRC_PEER_SENDER;
-    e->regmask = e->npad == 64 && c.peer_mode == BRC_PEER_SENDER && nL <= 2 && !e->general;
-    e->compact = e->npad == 64 && c.peer_mode == BRC_PEER_SENDER && !e->general;   // = lean_kernel<64, mode> (brc_step.h)
-    // wide exchange words per (key, type): connection peers send 8 count planes per link delay
-    const uint32_t xw = c.peer_mode == BRC_PEER_CONNECTION ? 8u * nL : xwords_wide(c.delay_model, c.delay_max, e->dm);
-    e->lds_bytes = e->wide ? lds_bytes_wide(e->npad, e->NK, e->nkw, xw,
-                                            spec, c.key_window, e->rs)
-                           : lds_bytes_per_wave(e->npad, e->NK, e->nkw, e->regmask ? 0u : nL, spec, c.key_window,
-                                                c.variants, e->rs, e->compact,
-                                                typed_list(e->compact, c.event_capacity != 0, (int)c.mode)) * WPB;
-    // wide kernel at 4 waves per SIMD (128 VGPRs): DM <= 8 without delay-code planes in registers (constant /
-    // slow-set delays), sender peers, and LDS for four workgroups per CU
-    // BRC_FLAG_WIDE_RECORDS: the instantiations with the record path (3 waves per SIMD, or 2 at DM = 16, only)
-    // BRC_FLAG_WIDE_VALUES: 3-bit value ids (V8), instantiated in the record form only -- such an engine takes what
-    // a BRC_FLAG_WIDE_RECORDS engine takes, and the two flags together select the same kernels
-    e->wide_val = e->wide && (c.flags & BRC_FLAG_WIDE_VALUES);
-    e->wide_rec = e->wide && (c.flags & (BRC_FLAG_WIDE_RECORDS | BRC_FLAG_WIDE_VALUES));
-    e->wide_wv4 = e->wide && e->dm <= 8 && !plane_model(c.delay_model) && c.peer_mode == BRC_PEER_SENDER &&
-                  e->lds_bytes <= 40u * 1024u && !e->wide_rec;
-    e->nval = e->wide_val ? 8u : value_ids(!e->compact && !e->wide);
-    e->cons_bytes = cons_bytes_per_item(spec, e->wide, e->lpi, e->msize, c.key_window, c.variants, e->nval);
-    // key-lifetime kernel (brc_life.h): NPAD = 64 consensus under a two-class delay model with D <= 8
-    // or per-link (uniform / geometric) delays with D <= 8, proposals from Philox or loaded, no event
-    // log, no Byzantine pattern.  BRC_KERNEL=step | life | auto (default): auto runs it whenever the
-    // configuration is eligible, except sender peers under per-link delays (the step kernel is faster
-    // there): since round 6 its two-class form simulates a step's new keys one per lane, 1.8-7x faster than
-    // the step kernel on cfg4.  A run it cannot take (injections, an event log, a stepped run)
-    // falls back to the step kernel.
-    // The lifetime kernel keeps no cells, so it also runs sender peers whose step-kernel cell store
-    // would not fit in the free device memory (the reference protocol's many-round runs: its phase
-    // leakage keeps ~1,000 keys of one instance live by round 8 at n = 64) and the key
-    // windows above 32 the lean step kernel does not take.
-    {
-        const char* kv = getenv("BRC_KERNEL");
-        const bool force_step = kv && strcmp(kv, "step") == 0, force_life = kv && strcmp(kv, "life") == 0;
-        e->life_pl = c.delay_model == BRC_DELAY_UNIFORM || c.delay_model == BRC_DELAY_GEOMETRIC;
-        e->life_lds = lds_bytes_life(e->NK, spec, c.key_window, c.variants, e->life_pl);
-        e->life_rw = (e->life_pl && c.delay_max > 8) ? LIFE_RW16 : LIFE_RW;
-        const bool eligible = e->npad == 64 && c.protocol == BRC_PROTO_CONSENSUS && !e->general &&
-                              c.proposals != BRC_PROPOSALS_NONE && c.event_capacity == 0 && c.byz_pattern == BRC_BYZ_NONE &&
-                              c.delay_max <= (e->life_pl ? 16u : 8u) && e->life_lds <= 160 * 1024 &&
-                              // per-link form: its HBM delivery ring is [RW][NK] bits per instance
-                              !(e->life_pl && c.key_window * c.variants > 32);
-        bool big = e->compact && c.key_window * c.variants > 32;          // the lean kernels take <= 32
-        // connection peers at NPAD = 64 with 8,192 key slots (Q * NV = 128): the step kernel's LDS carve
-        // (186 KB) exceeds a workgroup's 160 KB, the lifetime kernel's (HBM slot metadata) does not
-        const bool conn_big = !e->wide && c.peer_mode == BRC_PEER_CONNECTION && e->lds_bytes > 160 * 1024;
-        if (conn_big && eligible) big = true;
-        if (!big && e->compact && c.peer_mode == BRC_PEER_SENDER && hipSetDevice(c.device) == hipSuccess) {
-            // the step kernel's whole per-instance state (cells, slot metadata / generations / destinations,
-            // activity ring) against 90 % of the device's TOTAL memory: the choice depends on the
-            // configuration and the device model only, never on what else holds memory at the time (an
-            // engine whose state fits but cannot be allocated now fails brc_create with BRC_E_NOMEM)
-            size_t fr = 0, tot = 0;
-            const size_t keys = (size_t)c.instances * e->NK;
-            const size_t need = (size_t)e->nitems * (e->NK + 1) * 64 * 4 + keys * (8 + 4 + 8) +
-                                (size_t)e->nitems * e->rs * e->nkw * act_types(true, 1) * 8;
-            if (hipMemGetInfo(&fr, &tot) == hipSuccess && need > tot / 10 * 9) big = true;
-            (void)hipGetLastError();
-        }
-        const bool prefer_life = c.peer_mode == BRC_PEER_CONNECTION || !e->life_pl;
-        e->life_cfg = eligible && !force_step && (force_life || prefer_life || big);
-        e->step_ok = !big;
-        if (big && !e->life_cfg) {
-            g_create_err = c.key_window * c.variants > 32
-                ? "key windows above 32 at n in 33..64 with sender peers (128 with connection peers) run on the "
-                  "key-lifetime kernel only "
-                  "(consensus, Philox / loaded proposals, delay_max <= 8, constant or slow-set delays, no event log)"
-                : "the step kernel's cells do not fit in free device memory and the key-lifetime kernel cannot run "
-                  "this configuration";
-            delete e;
-            return BRC_E_INVALID;
-        }
-    }
-    if (c.flags & BRC_FLAG_WIDE_LIFE) {
-        // lifetime-only, as the "big" engines above: no cells, key-slot arrays or activity ring
-        e->life_pl = false;
-        e->life_rw = LIFE_RW;
-        e->life_lds = lds_bytes_life_wide(e->npad, e->NK, e->nkw, spec, c.key_window,
-                                          (c.flags & BRC_FLAG_LIFE_PATTERN) != 0);
-        e->life_cfg = true;
-        e->step_ok = false;
-        e->cons_bytes = 0;                               // the host masks / phase counters live in LDS for the whole run
-        if (e->life_lds > 160 * 1024) {
-            g_create_err = "BRC_FLAG_WIDE_LIFE: key_window * variants = " + std::to_string(c.key_window * c.variants) +
-                           " exceeds the wide key-lifetime kernel's LDS (lds " + std::to_string(e->life_lds) + " B of 163840)";
-            delete e;
-            return BRC_E_INVALID;
-        }
-    }
-    if ((e->step_ok && ((e->wide && e->nkw > (uint32_t)e->nkw_t) ||
-                        e->lds_bytes > 160 * 1024)) || e->nitems > 0x7FFFFFFFull * WPB) {
-        g_create_err = "configuration exceeds the kernel's LDS / key-slot limits (lds " + std::to_string(e->lds_bytes) + " B)";
-        delete e;
-        return BRC_E_INVALID;
-    }
     auto fail = [&](int code) {
         g_create_err = e->err.empty() ? std::string("brc_create: HIP call failed: ") + hipGetErrorString(hipGetLastError())
                                       : e->err;
@@ -669,26 +449,15 @@ int brc_create(const brc_config* cfg, void** out) {
     if (hipSetDevice(c.device) != hipSuccess) { g_create_err = "hipSetDevice failed"; delete e; return BRC_E_HIP; }
     if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) return fail(BRC_E_HIP);
     if (hipEventCreate(&e->ev0) != hipSuccess || hipEventCreate(&e->ev1) != hipSuccess) return fail(BRC_E_HIP);
-    const size_t cells = (size_t)e->nitems * e->rows * e->lpi;
-    const size_t keys = e->step_ok ? (size_t)c.instances * e->NK : 1;    // the step kernel's key-slot arrays
     struct A { void** p; size_t bytes; } allocs[] = {
-        {(void**)&e->cells, e->life_cfg ? 8 : cells * (e->compact ? 4 : 8)}, {(void**)&e->meta, keys * 8}, {(void**)&e->mgen, keys * 4},
-        {(void**)&e->kdst, keys * 8 * e->bw},
-        {(void**)&e->act, e->step_ok ? (size_t)e->nitems * e->rs * e->nkw * act_types(e->compact, e->ipw) * 8 : 8},
-        {(void**)&e->actany, (size_t)e->nitems * 4}, {(void**)&e->items, (size_t)e->nitems * sizeof(ItemState)},
-        {(void**)&e->inst, c.instances * sizeof(InstState)}, {(void**)&e->istats, c.instances * 32},
-        {(void**)&e->cons0, (size_t)e->nitems * e->lpi * 8}, {(void**)&e->cons1, (size_t)e->nitems * e->lpi * 8},
-        {&e->hmask, (size_t)e->nitems * e->cons_bytes}, {(void**)&e->inj_off, (size_t)e->nitems * 4},
-        {(void**)&e->inj_cnt, (size_t)e->nitems * 4}, {(void**)&e->byz, c.instances * e->bw * 8}, {(void**)&e->gcount, 64},
-        {(void**)&e->dparams, sizeof(Params)},
-        {(void**)&e->dbits, (e->compact && spec && e->step_ok) ? (size_t)e->nitems * e->nkw * 64 * 8 : 8},
-        {(void**)&e->dring, (e->life_cfg && e->life_pl) ? (size_t)e->nitems * e->life_rw * e->nkw * 64 * 8 : 8},
-        {(void**)&e->lmeta, (e->life_cfg && life_hbm_meta(c.key_window, e->life_pl)) ? (size_t)e->nitems * e->NK * 8 : 8},
-        // extra-SEND records: the non-lean narrow kernels only (the lean and wide kernels refuse extra SENDs)
-        // ... and the wide kernels' restricted ECHO / READY records, for engines created with BRC_FLAG_WIDE_RECORDS
-        {(void**)&e->xsend, e->wide_rec ? (size_t)e->nitems * XSEND_MAX * WREC_W * 8
-                                        : (e->compact || e->wide) ? 8 : (size_t)e->nitems * XSEND_MAX * 24},
-        {(void**)&e->xsn, (!e->wide_rec && (e->compact || e->wide)) ? 8 : (size_t)e->nitems * 4},
+        {(void**)&e->cells, e->cells_up_front ? e->cells_bytes : 8}, {(void**)&e->meta, e->meta_bytes},
+        {(void**)&e->mgen, e->mgen_bytes}, {(void**)&e->kdst, e->kdst_bytes}, {(void**)&e->act, e->act_bytes},
+        {(void**)&e->actany, e->item_u32_bytes}, {(void**)&e->items, e->items_bytes}, {(void**)&e->inst, e->inst_bytes},
+        {(void**)&e->istats, e->istats_bytes}, {(void**)&e->cons0, e->cons_rec_bytes}, {(void**)&e->cons1, e->cons_rec_bytes},
+        {&e->hmask, e->hmask_bytes}, {(void**)&e->inj_off, e->item_u32_bytes}, {(void**)&e->inj_cnt, e->item_u32_bytes},
+        {(void**)&e->byz, e->byz_bytes}, {(void**)&e->gcount, 64}, {(void**)&e->dparams, sizeof(Params)},
+        {(void**)&e->dbits, e->dbits_bytes}, {(void**)&e->dring, e->dring_bytes}, {(void**)&e->lmeta, e->lmeta_bytes},
+        {(void**)&e->xsend, e->xsend_bytes}, {(void**)&e->xsn, e->xsn_bytes},
     };
     for (auto& a : allocs)
         if (hipMalloc(a.p, std::max<size_t>(a.bytes, 8)) != hipSuccess) {
@@ -699,15 +468,13 @@ int brc_create(const brc_config* cfg, void** out) {
         if (hipMalloc(&e->events, (size_t)c.event_capacity * sizeof(brc_event)) != hipSuccess) return fail(BRC_E_NOMEM);
         if (hipMalloc(&e->event_count, 8) != hipSuccess) return fail(BRC_E_NOMEM);
     }
-    e->cells_ready = !e->life_cfg;
+    e->cells_ready = e->cells_up_front;
     e->last_life = e->life_cfg;       // brc_last_kernel before the first run: the kernel a fresh run launches
-    if (hipMemsetAsync(e->inj_off, 0, (size_t)e->nitems * 4, e->stream) != hipSuccess) return fail(BRC_E_HIP);
-    if (hipMemsetAsync(e->inj_cnt, 0, (size_t)e->nitems * 4, e->stream) != hipSuccess) return fail(BRC_E_HIP);
-    if (hipMemsetAsync(e->kdst, 0, keys * 8 * e->bw, e->stream) != hipSuccess) return fail(BRC_E_HIP);   // keys = 1: 8 B
+    if (hipMemsetAsync(e->inj_off, 0, e->item_u32_bytes, e->stream) != hipSuccess) return fail(BRC_E_HIP);
+    if (hipMemsetAsync(e->inj_cnt, 0, e->item_u32_bytes, e->stream) != hipSuccess) return fail(BRC_E_HIP);
+    if (hipMemsetAsync(e->kdst, 0, e->kdst_bytes, e->stream) != hipSuccess) return fail(BRC_E_HIP);
     // the lifetime kernel leaves its bitmap ring zero at exit
-    if (e->life_cfg && e->life_pl &&
-        hipMemsetAsync(e->dring, 0, (size_t)e->nitems * e->life_rw * e->nkw * 64 * 8, e->stream) != hipSuccess)
-        return fail(BRC_E_HIP);
+    if (e->has_dring && hipMemsetAsync(e->dring, 0, e->dring_bytes, e->stream) != hipSuccess) return fail(BRC_E_HIP);
     {
         std::vector<uint64_t> bm((size_t)c.instances * e->bw);
         for (uint64_t i = 0; i < c.instances; ++i)
@@ -767,15 +534,7 @@ int brc_inject(void* h, const brc_injection* list, size_t count) {
     if (!e || (!list && count)) return BRC_E_INVALID;
     if (e->pattern_active) { e->err = "explicit injections cannot be combined with byz_pattern"; return BRC_E_STATE; }
     const brc_config& c = e->cfg;
-    if (!e->step_ok && count && e->wide) {
-        e->err = "this engine runs on the wide key-lifetime kernel only (BRC_FLAG_WIDE_LIFE): no injections";
-        return BRC_E_UNSUPPORTED;
-    }
-    if (!e->step_ok && count) {
-        e->err = "this engine runs on the key-lifetime kernel only (its step-kernel state does not fit the device, "
-                 "or a key window above 32 at n in 33..64 with sender peers, of 128 with connection peers): no injections";
-        return BRC_E_UNSUPPORTED;
-    }
+    if (!e->step_ok && count) { e->err = life_only_why(*e, false); return BRC_E_UNSUPPORTED; }
     const uint64_t all = (c.n >= 64) ? ~0ull : ((1ull << c.n) - 1);
     std::vector<ItemState> its;
     std::vector<InstState> ist;
@@ -1109,18 +868,7 @@ int brc_run(void* h, uint32_t max_steps, uint32_t* running_left) {
     }
     int rc = upload_injections(e);
     if (rc) return rc;
-    if (!life && !e->step_ok && e->wide) {
-        e->err = "this engine runs on the wide key-lifetime kernel only (BRC_FLAG_WIDE_LIFE): a fresh run to completion, "
-                 "no injections, max_steps = 0 (brc_reset first)";
-        return BRC_E_UNSUPPORTED;
-    }
-    if (!life && !e->step_ok) {
-        e->err = "this engine runs on the key-lifetime kernel only (its step-kernel state does not fit, or a key "
-                 "window above 32 at n in 33..64 with sender peers, of 128 with connection peers): a fresh run to "
-                 "completion, no injections, "
-                 "max_steps = 0, value ids < 4 (brc_reset first)";
-        return BRC_E_UNSUPPORTED;
-    }
+    if (!life && !e->step_ok) { e->err = life_only_why(*e, true); return BRC_E_UNSUPPORTED; }
     if (!life) {
         rc = ensure_cells(e);
         if (rc) return rc;
@@ -1128,7 +876,7 @@ int brc_run(void* h, uint32_t max_steps, uint32_t* running_left) {
     if (gen_clear) {
         rc = fill_cells(e);
         if (rc) return rc;
-        HIPCHK(e, hipMemsetAsync(e->mgen, 0, (size_t)c.instances * e->NK * 4, e->stream));
+        HIPCHK(e, hipMemsetAsync(e->mgen, 0, e->mgen_bytes, e->stream));
         e->gen_base = 0;
     }
     Params P;
@@ -1161,28 +909,14 @@ int brc_run(void* h, uint32_t max_steps, uint32_t* running_left) {
     P.inj = e->inj; P.inj_off = e->inj_off; P.inj_cnt = e->inj_cnt; P.byz = e->byz; P.prop = e->prop;
     P.events = e->events; P.event_count = e->event_count; P.gcount = e->gcount; P.dbits = e->dbits;
     P.dring = e->dring; P.lmeta = e->lmeta; P.xsend = e->xsend; P.xsn = e->xsn;
-    const uint32_t blocks = e->wide ? (uint32_t)e->nitems : (uint32_t)((e->nitems + WPB - 1) / WPB);
     e->hparams = P;
     HIPCHK(e, hipMemcpyAsync(e->dparams, &e->hparams, sizeof(Params), hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipMemsetAsync(e->gcount + 6, 0, 8, e->stream));   // instances still running after this launch
     HIPCHK(e, hipEventRecord(e->ev0, e->stream));   // times the step kernel alone
-    const int kmode = c.peer_mode == BRC_PEER_CONNECTION ? KMODE_CONN : e->general ? KMODE_XREF : (int)c.mode;
     e->fresh = false;
     e->last_life = life;
-    if (life && e->wide) {
-        rc = launch_life_wide(e->npad, kmode, (c.flags & BRC_FLAG_LIFE_PATTERN) != 0, (uint32_t)e->nitems, e->life_lds,
-                              e->stream, e->dparams);
-        e->life_done = true;
-    } else if (life) {
-        rc = launch_life(kmode, e->life_pl, e->life_rw == LIFE_RW16, c.key_window >= 64,
-                         life_hbm_meta(c.key_window, e->life_pl), (uint32_t)e->nitems,
-                         e->life_lds, e->stream, e->dparams);
-        e->life_done = true;
-    } else {
-        rc = e->regmask ? launch_step_64r(e->dm, c.event_capacity != 0, kmode, blocks, e->lds_bytes, e->stream, e->dparams)
-                        : launch_step(e->npad, e->dm, c.event_capacity != 0, kmode, e->wide_wv4, e->wide_rec, e->wide_val, blocks,
-                                      e->lds_bytes, e->stream, e->dparams);
-    }
+    if (life) e->life_done = true;
+    rc = launch_kernel(e, life, e->dparams);
     if (rc == BRC_E_INVALID) { e->err = "no kernel instantiation"; return rc; }
     if (rc) { e->err = std::string("step kernel launch: ") + hipGetErrorString(hipGetLastError()); return rc; }
     HIPCHK(e, hipEventRecord(e->ev1, e->stream));
