@@ -127,6 +127,7 @@ typedef struct {
     cons_t cons[OR_MAXN];
     uint8_t delay[OR_MAXN][OR_MAXN];
     int err, overflow;
+    int bcast;                      /* the caller's oracle_result has the `bcasts` list (oracle_run_broadcasts) */
 } sim_t;
 
 static uint64_t kh(uint32_t kp, uint32_t s) {
@@ -217,9 +218,29 @@ static void net_send(sim_t* S, uint32_t src, uint32_t dst, uint32_t type, int ke
     b->v[b->n++] = m;
 }
 
+/* One call that sends (a net_broadcast, or an OR_ACT_BYZ with its destination set): a `bcasts` row if it put
+ * a message on a link (brc_oracle.h). */
+typedef struct { uint64_t sent0; uint32_t first; } call_t;
+
+static call_t call_begin(const sim_t* S, uint32_t src, uint32_t type, int key) {
+    const bits_t* sent = &S->keys[key].sent[(type - 1) * S->n + src];
+    call_t c = {S->res->msgs_sent, !(sent->w[0] | sent->w[1] | sent->w[2] | sent->w[3])};
+    return c;
+}
+
+static void call_end(sim_t* S, call_t c, uint32_t src, uint32_t type, int key) {
+    const key_t_* k = &S->keys[key];
+    const uint64_t links = S->res->msgs_sent - c.sent0;
+    if (!S->bcast || !links) return;
+    uint32_t ev[8] = {S->t, src, type, k->kp, k->s, (uint32_t)k->value, c.first, (uint32_t)links};
+    push_event(S->res->bcasts, S->res->bcast_cap, &S->res->n_bcast, 8, ev);
+}
+
 /* base/broadcast.py:17-40: one message to every peer, self included (:30). */
 static void net_broadcast(sim_t* S, uint32_t src, uint32_t type, int key) {
+    const call_t c = call_begin(S, src, type, key);
     for (uint32_t d = 0; d < S->n; ++d) net_send(S, src, d, type, key);
+    call_end(S, c, src, type, key);
 }
 
 static void cons_send_key(sim_t* S, uint32_t node, uint32_t s, int32_t value) {
@@ -465,8 +486,10 @@ static void do_action(sim_t* S, const oracle_action* a) {
     case OR_ACT_BYZ: {
         int key = key_find(S, a->kp, a->s);
         if (key < 0) { S->err = -7; return; }
+        const call_t c = call_begin(S, a->node, a->type, key);
         for (uint32_t d = 0; d < S->n; ++d)
             if ((a->dst[d >> 6] >> (d & 63)) & 1ull) net_send(S, a->node, d, a->type, key);
+        call_end(S, c, a->node, a->type, key);
         break;
     }
     default:
@@ -474,14 +497,15 @@ static void do_action(sim_t* S, const oracle_action* a) {
     }
 }
 
-int oracle_run(const oracle_spec* sp, oracle_result* res) {
+static int run(const oracle_spec* sp, oracle_result* res, int bcast) {
     if (!sp || !res || sp->n == 0 || sp->n > OR_MAXN || sp->dmax < 1 || sp->dmax > 16 || sp->nv < 1)
         return -1;
     sim_t* S = (sim_t*)calloc(1, sizeof(sim_t));
     if (!S) return -2;
-    S->sp = sp; S->res = res; S->n = sp->n; S->f = sp->f; S->D = sp->dmax;
+    S->sp = sp; S->res = res; S->n = sp->n; S->f = sp->f; S->D = sp->dmax; S->bcast = bcast;
     res->status = 0; res->t_stop = 0; res->msgs_sent = 0; res->arrivals = 0;
     res->n_deliver = res->n_decide = res->n_send = 0;
+    if (bcast) res->n_bcast = 0;
     res->cell_steps = 0;
     for (uint32_t s = 0; s < S->n; ++s)
         for (uint32_t d = 0; d < S->n; ++d)
@@ -538,3 +562,9 @@ int oracle_run(const oracle_spec* sp, oracle_result* res) {
     free(S);
     return err;
 }
+
+/* The result as it was before the `bcasts` list: nothing from that member on is read or written, so a caller built
+ * against the shorter struct keeps working. */
+int oracle_run(const oracle_spec* sp, oracle_result* res) { return run(sp, res, 0); }
+
+int oracle_run_broadcasts(const oracle_spec* sp, oracle_result* res) { return run(sp, res, 1); }

@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "liboracle.so")
 ACT = {"propose": 1, "brb_send": 2, "byz_key": 3, "byz": 4, "deliver": 5}
 STATUS = {1: "done", 2: "quiescent", 3: "stepcap", 4: "overflow"}
 PEER_MODES = {"sender": 0, "connection": 1}
+FIRST_CAP = 65536          # rows of each list's first buffer; a run with more is repeated with bigger ones
 MODES = {"brb": 0, "consensus": 1, "spec": 2, "spec_brb": 3, "beb": 4, "beb_consensus": 5}
 
 
@@ -40,7 +41,9 @@ class _Result(ctypes.Structure):
                 ("decide", ctypes.POINTER(ctypes.c_uint32)), ("decide_cap", ctypes.c_size_t),
                 ("n_decide", ctypes.c_size_t),
                 ("sends", ctypes.POINTER(ctypes.c_uint32)), ("send_cap", ctypes.c_size_t),
-                ("n_send", ctypes.c_size_t), ("cell_steps", ctypes.c_uint64)]
+                ("n_send", ctypes.c_size_t), ("cell_steps", ctypes.c_uint64),
+                ("bcasts", ctypes.POINTER(ctypes.c_uint32)), ("bcast_cap", ctypes.c_size_t),
+                ("n_bcast", ctypes.c_size_t)]
 
 
 _lib = None
@@ -54,6 +57,8 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         L.oracle_run.argtypes = [ctypes.POINTER(_Spec), ctypes.POINTER(_Result)]
         L.oracle_run.restype = ctypes.c_int
+        L.oracle_run_broadcasts.argtypes = L.oracle_run.argtypes
+        L.oracle_run_broadcasts.restype = ctypes.c_int
         L.oracle_delay.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
                                    ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
                                    ctypes.c_uint32]
@@ -101,10 +106,8 @@ def expand_actions(actions, n):
     return out
 
 
-def run(spec, light=False, kinds=("deliver", "decide", "send")):
-    """Run one instance of ``spec`` (harness format) and return the harness result format.
-    ``light``: status and counters only (no event lists; one C call, no Python conversion).
-    ``kinds``: the event lists to return (the others come back empty; their counts are exact)."""
+def c_spec(spec):
+    """The oracle_spec of ``spec`` (harness format); it points into the action array, returned with it."""
     acts = expand_actions(spec.get("actions", []), spec["n"])
     arr = (_Action * max(1, len(acts)))()
     for i, a in enumerate(acts):
@@ -124,16 +127,28 @@ def run(spec, light=False, kinds=("deliver", "decide", "send")):
                g=spec["g"], step_cap=spec.get("step_cap", 10000), n_actions=len(acts),
                byz=_mask4(byz), actions=arr, coin_seed=spec.get("coin_seed", 0), window=spec.get("window", 0),
                peer_mode=PEER_MODES[spec.get("peer_mode", "sender")])
-    names = ("deliver", "decide", "send")
-    caps = [0 if light or k not in kinds else 65536 for k in names]
+    return sp, arr
+
+
+def run(spec, light=False, kinds=("deliver", "decide", "send")):
+    """Run one instance of ``spec`` (harness format) and return the harness result format.
+    ``light``: status and counters only (no event lists; one C call, no Python conversion).
+    ``kinds``: the event lists to return (the others come back empty; their counts are exact).
+    "broadcasts" (not a default kind; its list and count are returned only when asked for): one row
+    [t, src, type, kp, s, value id, first, links] per call that put a message on a link (brc_oracle.h)."""
+    sp, _actions = c_spec(spec)
+    names = ("deliver", "decide", "send", "broadcasts")
+    caps = [0 if light or k not in kinds else FIRST_CAP for k in names]
     while True:
-        bufs = [(ctypes.c_uint32 * (c * w))() for c, w in zip(caps, (4, 4, 5))]
+        bufs = [(ctypes.c_uint32 * (c * w))() for c, w in zip(caps, (4, 4, 5, 8))]
         res = _Result(deliver=bufs[0], deliver_cap=caps[0], decide=bufs[1], decide_cap=caps[1],
-                      sends=bufs[2], send_cap=caps[2])
-        rc = lib().oracle_run(ctypes.byref(sp), ctypes.byref(res))
+                      sends=bufs[2], send_cap=caps[2], bcasts=bufs[3], bcast_cap=caps[3])
+        # oracle_run leaves the fourth list alone (and costs nothing for it); its twin fills it
+        entry = lib().oracle_run_broadcasts if caps[3] else lib().oracle_run
+        rc = entry(ctypes.byref(sp), ctypes.byref(res))
         if rc != 0:
             raise RuntimeError("oracle_run failed: %d" % rc)
-        got = (res.n_deliver, res.n_decide, res.n_send)
+        got = (res.n_deliver, res.n_decide, res.n_send, res.n_bcast)
         if light or all(k not in kinds or n <= c for k, n, c in zip(names, got, caps)):
             break
         caps = [2 * n if k in kinds and n > c else c for k, n, c in zip(names, got, caps)]
@@ -150,8 +165,12 @@ def run(spec, light=False, kinds=("deliver", "decide", "send")):
     values = spec.get("values")
     if values is not None:
         dec = [[t, nd, r, values[v]] for t, nd, r, v in dec]
-    return {"status": STATUS.get(res.status), "t_stop": res.t_stop, "msgs_sent": res.msgs_sent,
-            "arrivals": res.arrivals, "cell_steps": res.cell_steps,
-            "counts": {"deliver": res.n_deliver, "decide": res.n_decide, "send": res.n_send},
-            "events": {"deliver": rows(bufs[0], res.n_deliver, 4, "deliver"), "decide": dec,
-                       "send": rows(bufs[2], res.n_send, 5, "send")}}
+    out = {"status": STATUS.get(res.status), "t_stop": res.t_stop, "msgs_sent": res.msgs_sent,
+           "arrivals": res.arrivals, "cell_steps": res.cell_steps,
+           "counts": {"deliver": res.n_deliver, "decide": res.n_decide, "send": res.n_send},
+           "events": {"deliver": rows(bufs[0], res.n_deliver, 4, "deliver"), "decide": dec,
+                      "send": rows(bufs[2], res.n_send, 5, "send")}}
+    if "broadcasts" in kinds:
+        out["counts"]["broadcasts"] = res.n_bcast
+        out["events"]["broadcasts"] = rows(bufs[3], res.n_bcast, 8, "broadcasts")
+    return out

@@ -113,6 +113,35 @@ def instance_events(evs, specs):
     return per
 
 
+def instance_event_tuples(evs, count):
+    """Engine.events() split per instance into full records (t, kind, node, type, a, b, value id), device order:
+    every kind (L.EV_COPY included) and every field, the value id that instance_events drops among them."""
+    per = [[] for _ in range(count)]
+    for ev in evs:
+        per[ev[0]].append(tuple(ev[1:]))
+    return per
+
+
+def oracle_event_tuples(sp, exp):
+    """The records instance_event_tuples() must hold for spec sp, from the oracle's run exp of it
+    (oracle.run(dict(sp, values=None), kinds=("deliver", "decide", "broadcasts")): decide rows carry value ids).
+    A broadcast row [t, src, type, kp, s, value, first, links] is a SEND event when first, else a COPY event under
+    connection peers and none under sender peers; a DELIVER carries the value id of its key, looked up in the
+    key table the broadcast rows give (a key no row mentions cannot be delivered); a DECIDE carries its value
+    id twice (b and value)."""
+    conn = sp.get("peer_mode") == "connection"
+    value, out = {}, []
+    for t, src, typ, kp, s, v, first, _links in exp["events"]["broadcasts"]:
+        assert value.setdefault((kp, s), v) == v, (sp.get("name"), kp, s)
+        if first or conn:
+            out.append((t, L.EV_SEND if first else L.EV_COPY, src, typ, kp, s, v))
+    for t, node, kp, s in exp["events"]["deliver"]:
+        out.append((t, L.EV_DELIVER, node, 0, kp, s, value[(kp, s)]))
+    for t, node, rnd, v in exp["events"]["decide"]:
+        out.append((t, L.EV_DECIDE, node, 0, rnd, v, v))
+    return out
+
+
 def mask_words(specs, garbage=None):
     """brc_load_byzantine's argument for the specs' own Byzantine lists: [instance][(n + 63) // 64] u64 words,
     the caller's stride (the engine keeps NPAD / 64 words per instance).  garbage: a seed; every bit at or
