@@ -83,6 +83,11 @@ inline int make_plan(const brc_config& c, const PlanEnv& env, Plan* out, std::st
                                                    : nullptr;
         if (why) return refuse(why);
     }
+    // every fault bound 0 .. n - 1 runs (the kernels compute n - f unsigned); f = n would leave no replica to count.
+    // Named here, for a committee size in range; the range check below keeps its own f >= n
+    if (c.n >= 1 && c.n <= 256 && c.f >= c.n)
+        return refuse("the fault bound f = " + std::to_string(c.f) + " must be below n = " + std::to_string(c.n) +
+                      " (f: 0 .. n - 1)");
     if (c.n < 1 || c.n > 256 || c.instances == 0 || c.delay_max < 1 || c.delay_max > 16 ||
         c.step_cap > STEP_LIMIT || c.peer_mode > BRC_PEER_CONNECTION ||
         (c.peer_mode == BRC_PEER_CONNECTION && c.mode != BRC_MODE_REFERENCE) ||
@@ -107,6 +112,10 @@ inline int make_plan(const brc_config& c, const PlanEnv& env, Plan* out, std::st
          c.mode != BRC_MODE_REFERENCE) ||
         (c.n > 64 && c.mode == BRC_MODE_SPEC && c.variants != 1))
         return refuse("invalid configuration (see include/brc.h field ranges)");
+    // (a backstop behind the two checks above: nothing below this line may ever see f >= n)
+    if (c.f >= c.n)
+        return refuse("the fault bound f = " + std::to_string(c.f) + " must be below n = " + std::to_string(c.n) +
+                      " (f: 0 .. n - 1)");
     if ((c.flags & BRC_FLAG_WIDE_RECORDS) && (c.n <= 64 || c.peer_mode != BRC_PEER_SENDER))
         return refuse(c.n <= 64 ? "BRC_FLAG_WIDE_RECORDS is for the wide kernels (n > 64): the narrow kernels take restricted "
                                   "ECHO / READY records without a flag (n <= 32, or BRC_FLAG_GENERAL_KEYS at n in 33..64)"

@@ -79,7 +79,10 @@ enum { BRC_EV_DELIVER = 1, BRC_EV_DECIDE = 2, BRC_EV_SEND = 3, BRC_EV_COPY = 4 }
 
 typedef struct {
     uint32_t n;               /* replicas per instance, self included (1..256) */
-    uint32_t f;               /* fault bound: thresholds (n+f)/2, f+1, 2f+1, n-f+1 */
+    uint32_t f;               /* fault bound: thresholds (n+f)/2, f+1, 2f+1, n-f+1.  Every value 0..n-1 is held to the
+                               * oracle on every kernel (f >= n: BRC_E_INVALID, the reason names f): at 0 the slow set is
+                               * empty, at n-1 one replica is fast, and once 2f+1 exceeds the honest replicas no READY
+                               * quorum is reachable, so the reference and SPEC broadcasts deliver nothing */
     uint32_t protocol;        /* BRC_PROTO_* */
     uint32_t peer_mode;       /* BRC_PEER_SENDER / BRC_PEER_CONNECTION (core/brbroadcast.py:69-71) */
     uint64_t instances;       /* instances owned by this engine */

@@ -197,6 +197,39 @@ int main() {
         c = base_config(64, CONS, REF, CONN, BRC_DELAY_UNIFORM, 16, 8, 1, PHILOX); emit_envs(c);
         c = base_config(64, CONS, REF, SND, BRC_DELAY_GEOMETRIC, 16, 8, 1, PHILOX); emit_envs(c);
     }
+    // 5. the fault bound's ends on every kernel family of tests/fault_bound_workloads.py: f = 0 and f = n - 1 run,
+    //    f = n and f = n + 1 are refused by name
+    for (uint32_t n : {1u, 2u, 3u, 4u, 33u, 64u, 65u, 256u}) {
+        const uint32_t BEB = BRC_MODE_BEB, SLOW = BRC_DELAY_SLOWSET, UNIF = BRC_DELAY_UNIFORM;
+        struct Fam { brc_config c; const char* env; };
+        Fam fams[12];
+        size_t nf = 0;
+        if (n <= 32) {
+            fams[nf++] = {base_config(n, BRC_PROTO_BRB, REF, SND, SLOW, 4, 8, 1, BRC_PROPOSALS_NONE), nullptr};
+            for (uint32_t m : {REF, SPEC, BEB}) fams[nf++] = {base_config(n, CONS, m, SND, SLOW, 4, 8, 1, PHILOX), nullptr};
+            fams[nf++] = {base_config(n, CONS, REF, CONN, UNIF, 4, 8, 1, PHILOX), nullptr};
+        } else if (n <= 64) {
+            for (uint32_t m : {REF, SPEC, BEB}) {
+                fams[nf++] = {base_config(n, CONS, m, SND, SLOW, 8, 8, 1, PHILOX), "step"};     // lean
+                fams[nf++] = {base_config(n, CONS, m, SND, SLOW, 8, 8, 1, PHILOX), "life"};     // two-class lifetime
+            }
+            fams[nf++] = {base_config(n, CONS, REF, SND, SLOW, 4, 8, 1, PHILOX, BRC_FLAG_GENERAL_KEYS), "step"};
+            fams[nf++] = {base_config(n, CONS, REF, CONN, SLOW, 4, 8, 1, PHILOX), "step"};
+            fams[nf++] = {base_config(n, CONS, REF, CONN, SLOW, 4, 8, 1, PHILOX), "life"};
+            fams[nf++] = {base_config(n, CONS, SPEC, SND, UNIF, 12, 8, 1, PHILOX), "life"};     // per-link lifetime
+            fams[nf++] = {base_config(n, CONS, REF, CONN, UNIF, 12, 8, 1, PHILOX), "life"};
+        } else {
+            for (uint32_t m : {REF, SPEC, BEB}) {
+                fams[nf++] = {base_config(n, CONS, m, SND, SLOW, 8, 8, 1, PHILOX), nullptr};    // wide step
+                fams[nf++] = {base_config(n, CONS, m, SND, SLOW, 8, 8, 1, PHILOX, BRC_FLAG_WIDE_LIFE), nullptr};
+            }
+            fams[nf++] = {base_config(n, CONS, REF, SND, SLOW, 8, 4, 2, PHILOX, BRC_FLAG_WIDE_RECORDS), nullptr};
+            fams[nf++] = {base_config(n, CONS, REF, SND, SLOW, 8, 4, 2, PHILOX, BRC_FLAG_WIDE_LIFE | BRC_FLAG_LIFE_PATTERN,
+                                      BRC_BYZ_EQUIVOCATE), nullptr};
+        }
+        for (size_t i = 0; i < nf; ++i)
+            for (uint32_t f : {0u, n - 1, n, n + 1}) { brc_config c = fams[i].c; c.f = f; emit(c, fams[i].env); }
+    }
     fprintf(stderr, "%zu configurations\n", emitted);
     return 0;
 }

@@ -69,7 +69,8 @@ def test_every_refusal_reason_is_produced(cases):
     # the planner's texts: every literal but the BRC_KERNEL values, the closing fragments of the two reasons that
     # carry a number, and the four lifetime-only texts of brc_inject / brc_run (life_only_why: no brc_create refusal)
     texts = [t for t in planner_reason_literals() if len(t) > 16 and not t.startswith("this engine runs on")]
-    assert len(texts) == 30, texts
+    # (30 reasons, and the two fragments of the reason that names f, which the planner states at both of its f >= n checks)
+    assert len(texts) == 34 and len(set(texts)) == 32, texts
     for t in texts:
         hit = any(t in r for r in reasons)
         assert hit != (t in UNREACHABLE), t
@@ -106,6 +107,44 @@ def test_every_kernel_family_is_selected(cases):
             names = set(fam)
             seen |= {k for k, v in fam.items() if v}
     assert seen == names, sorted(names - seen)
+
+
+FAULT_BOUND_NS = (1, 2, 3, 4, 33, 64, 65, 256)
+
+
+def test_fault_bound_ends(cases):
+    """f = n and f = n + 1 are refused with a reason that names f and both numbers; f = 0 and f = n - 1 are planned on
+    every kernel family tests/fault_bound_workloads.py uses at that committee size (plan_dump.cpp, part 5)."""
+    narrow = {"npad4"}
+    mid = {"lean64-regmask", "general64", "connection64", "life-two-class", "life-dm16"}     # (per-link delays up to 12)
+    wide = {"wide-wv4", "wide-records", "wide-life", "wide-life-pattern"}
+    for n in FAULT_BOUND_NS:
+        for f in (n, n + 1):
+            rows = [(c, rc, why) for c, _, _, rc, why, _ in cases if c["n"] == n and c["f"] == f]
+            assert len(rows) >= 5, (n, f)
+            for c, rc, why in rows:
+                # (the pattern flag's own conditions are checked first and name their field)
+                if rc == L.E_INVALID and why.startswith("BRC_FLAG_LIFE_PATTERN"):
+                    continue
+                assert rc == L.E_INVALID and why == "the fault bound f = %d must be below n = %d (f: 0 .. n - 1)" % (f, n), (c, why)
+        for f in (0, n - 1):
+            seen, modes, protocols = set(), set(), set()
+            for c, _, _, rc, why, p in cases:
+                if c["n"] == n and c["f"] == f and rc == L.OK:
+                    seen |= {k for k, v in families(c, p).items() if v}
+                    modes.add((c["mode"], c["peer_mode"], bool(p["life_cfg"])))
+                    protocols.add(c["protocol"])
+            want = narrow if n <= 32 else mid if n <= 64 else wide
+            assert seen >= want, (n, f, sorted(want - seen))
+            ref, spec, beb = L.MODE_REFERENCE, L.MODE_SPEC, L.MODE_BEB
+            assert modes >= {(m, L.PEER_SENDER, False) for m in (ref, spec, beb)}, (n, f, modes)
+            if n <= 64:
+                assert (ref, L.PEER_CONNECTION, False) in modes, (n, f)
+            if n > 32:
+                assert modes >= {(m, L.PEER_SENDER, True) for m in (ref, spec, beb)}, (n, f, modes)
+            assert n > 32 or protocols == {L.PROTO_BRB, L.PROTO_CONSENSUS}, (n, f)
+    # no configuration with f >= n is planned anywhere in the grid
+    assert not [c for c, _, _, rc, _, _ in cases if rc == L.OK and c["f"] >= c["n"]]
 
 
 def test_plan_invariants(cases):

@@ -75,6 +75,48 @@ def test_oracle_spec_matches_model_with_every_variant(chunk):
         _check(sp)
 
 
+def _fault_bound_specs(seed, count):
+    """f from the whole range 0 .. n - 1 and committees down to n = 1 (the draws above stop at (n - 1) // 3 and n = 4):
+    the four thresholds where n - f is 1 or 2, where 2 f + 1 exceeds n, and with n + f of both parities.  SPEC above
+    its fault bound may flip coins for ever, so the step cap is low; a stop there is compared like any other."""
+    rng = random.Random(seed)
+    out = []
+    for i in range(count):
+        n = rng.choice([1, 2, 3, 1, 2, 3, 4, 5, 7, 10])
+        f = rng.randint(0, n - 1)
+        model = rng.randint(0, 3)
+        dmax = rng.randint(1, 5) if model else 1
+        window = rng.choice([2, 4, 8])
+        g = rng.getrandbits(20)
+        byz = rng.sample(range(n), rng.randint(0, min(f, n - 1, 2))) if rng.random() < 0.4 else []
+        kind = rng.random()
+        if kind < 0.25:
+            sends = [(rng.randint(0, 5), o, q) for o in range(n) if o not in byz for q in range(rng.randint(0, 2))]
+            sp = S.spec_brb_spec(n, f, rng.getrandbits(40), model, dmax, g, sends, window=window, byzantine=byz)
+        elif kind < 0.4:
+            sends = [(rng.randint(0, 5), o, q) for o in range(n) if o not in byz for q in range(rng.randint(0, 2))]
+            sp = S.beb_spec(n, rng.getrandbits(40), model, dmax, g, sends, byzantine=byz)
+            sp["f"] = f                                   # (the slow set's size; best-effort broadcast has no quorum)
+        else:
+            sp = S.spec_cons_spec(n, f, rng.getrandbits(40), model, dmax, g, round_cap=rng.randint(1, 3), window=window,
+                                  coin_seed=rng.getrandbits(40), byzantine=byz, step_cap=150)
+        sp["name"] = "specfault/%d" % i
+        out.append(sp)
+    return out
+
+
+@pytest.mark.parametrize("chunk", range(3))
+def test_oracle_spec_matches_model_over_the_whole_fault_range(chunk):
+    specs = _fault_bound_specs(3000 + chunk, 60)
+    assert sum(sp["n"] <= 3 for sp in specs) >= 20 and sum(sp["f"] > (sp["n"] - 1) // 3 for sp in specs) >= 15
+    assert any(sp["f"] == sp["n"] - 1 and sp["n"] > 1 for sp in specs) and any(sp["f"] == 0 for sp in specs)
+    ended = 0
+    for sp in specs:
+        r = _check(sp)
+        ended += any(e[2] == 1 and e[4] >= 1 for e in r["events"]["send"])
+    assert ended >= 10, ended                             # phase ends happen: the draws are not all stalls
+
+
 def test_spec_coin_rounds_happen():
     """With an even split the phase-2 tallies stay at or below f, so the common coin decides the
     next estimate; every honest replica still decides, and all decide the same value."""
