@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libbrc_hip.so"
 LIB_PATH = os.environ.get("BRC_LIB") or os.path.join(_HERE, LIB_NAME)   # BRC_LIB: dev A/B builds only
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 OK, E_INVALID, E_NOMEM, E_HIP, E_UNSUPPORTED, E_STATE = 0, -1, -2, -3, -4, -5
 ERRORS = {E_INVALID: "invalid argument", E_NOMEM: "out of memory", E_HIP: "HIP error",
@@ -24,6 +24,7 @@ FLAG_WIDE_VALUES = 4        # brc.h BRC_FLAG_WIDE_VALUES (ABI v9)
 FLAG_WIDE_WINDOWS = 8       # brc.h BRC_FLAG_WIDE_WINDOWS (ABI v10)
 FLAG_WIDE_LIFE = 16         # brc.h BRC_FLAG_WIDE_LIFE (ABI v11)
 FLAG_LIFE_PATTERN = 32      # brc.h BRC_FLAG_LIFE_PATTERN (ABI v12)
+FLAG_LIFE_VALUES = 128      # brc.h BRC_FLAG_LIFE_VALUES (ABI v13; bit 64 is unassigned)
 PEER_SENDER, PEER_CONNECTION = 0, 1
 DELAY_CONST, DELAY_UNIFORM, DELAY_SLOWSET, DELAY_GEOMETRIC = 0, 1, 2, 3
 PROPOSALS_NONE, PROPOSALS_PHILOX, PROPOSALS_LOADED = 0, 1, 2

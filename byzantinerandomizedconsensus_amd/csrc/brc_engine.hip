@@ -254,6 +254,8 @@ static int launch_kernel(const Engine* e, bool life, const Params* P) {
     hipStream_t st = e->stream;
     if (life && e->wide) {
         // the wide key-lifetime kernel (BRC_FLAG_WIDE_LIFE): one workgroup of NPAD threads per instance
+        if (e->life_val) return npad == 128 ? launch_life_128v(mode, e->life_pat, items, e->life_lds, st, P)
+                              : npad == 256 ? launch_life_256v(mode, e->life_pat, items, e->life_lds, st, P) : BRC_E_INVALID;
         if (e->life_pat) return npad == 128 ? launch_life_128p(mode, items, e->life_lds, st, P)
                               : npad == 256 ? launch_life_256p(mode, items, e->life_lds, st, P) : BRC_E_INVALID;
         return npad == 128 ? launch_life_128(mode, items, e->life_lds, st, P)
@@ -507,7 +509,8 @@ int brc_load_proposals(void* h, const int8_t* proposals) {
         }
         wide_ids = wide_ids || proposals[i] > 3;
     }
-    e->values_wide = wide_ids;               // the lifetime kernel keeps 2-bit value ids
+    // the lifetime kernels keep 2-bit value ids, but for the wide one under BRC_FLAG_LIFE_VALUES
+    e->values_wide = wide_ids && !e->life_val;
     if (!e->prop) HIPCHK(e, hipMalloc(&e->prop, bytes));
     HIPCHK(e, hipMemcpyAsync(e->prop, proposals, bytes, hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));

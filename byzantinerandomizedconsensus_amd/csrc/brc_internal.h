@@ -129,6 +129,10 @@ int launch_life_256(int mode, uint32_t blocks, uint32_t lds, hipStream_t s, cons
 // ... and of the pattern form (brc_kern_life128p.hip / brc_kern_life256p.hip); mode: BRC_MODE_REFERENCE / BRC_MODE_BEB
 int launch_life_128p(int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
 int launch_life_256p(int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
+// ... and of the 3-bit value-id form (brc_kern_life128v.hip / brc_kern_life256v.hip; BRC_FLAG_LIFE_VALUES); mode:
+// BRC_MODE_REFERENCE / BRC_MODE_BEB, pat: the pattern form
+int launch_life_128v(int mode, bool pat, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
+int launch_life_256v(int mode, bool pat, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P);
 
 // Step-kernel launchers, one translation unit per replica-set width NPAD (brc_kern_<NPAD>.hip).
 // Return 0 on success, BRC_E_INVALID when no instantiation matches (dm), BRC_E_HIP on a launch error.

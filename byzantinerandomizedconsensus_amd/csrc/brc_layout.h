@@ -83,7 +83,8 @@ constexpr uint32_t WREC_W = 5;
 // Consensus value ids (core/byzantinerandomizedconsensus.py:57-60 keys its tables by payload string;
 // id 0 is str(NONE) == "-1"): 2 bits (3 strings + "-1") on the lean, wide and key-lifetime kernels,
 // 3 bits (7 strings + "-1") on the other narrow kernels (NPAD <= 32, and connection peers) and on the wide
-// kernels of an engine created with BRC_FLAG_WIDE_VALUES (brc_step_wide.h V8: the planner sets nval itself).
+// kernels of an engine created with BRC_FLAG_WIDE_VALUES (brc_step_wide.h V8: the planner sets nval itself) and on the
+// wide key-lifetime kernel of one created with BRC_FLAG_LIFE_VALUES (brc_life_wide.h V8).
 BRC_HD constexpr uint32_t value_ids(bool narrow_full) { return narrow_full ? 8u : 4u; }
 
 // u64 words of a wave's consensus LDS area: REFERENCE hm[nval][64] T; SPEC [seen[Q][64] T +] cnt[Q][64] u32
@@ -199,10 +200,12 @@ constexpr uint32_t LIFE_RW16 = 64;
 // pat (the pattern form, BRC_FLAG_LIFE_PATTERN): four class bitmaps per key word instead of two (+ 16 nkw), and
 //   pbyz[4] u64 (the Byzantine mask) | pcnt[8] u32 (class sizes per parity) | oA[2 NPAD], oB[2 NPAD] u8 (the
 //   out-classes' delivery steps of the pattern keys)
+// v8 (3-bit value ids, BRC_FLAG_LIFE_VALUES): val[NK] u8 (the slots' value ids) at the end; host-mask planes 4..7
+//   stay in the HBM buffer, as on the wide step kernel
 BRC_HD inline uint32_t lds_bytes_life_wide(int npad, uint32_t NK, uint32_t nkw, bool spec, uint32_t Q,
-                                           bool pat = false) {
+                                           bool pat = false, bool v8 = false) {
     return 16 * nkw + 8 * cons_words_wide(spec, (uint32_t)npad, Q) + 4 * NK + 4 * (4 * LIFE_RW + 16) + 2 * NK +
-           Q * (uint32_t)npad + (pat ? 16 * nkw + 64 + 4 * (uint32_t)npad : 0u);
+           Q * (uint32_t)npad + (pat ? 16 * nkw + 64 + 4 * (uint32_t)npad : 0u) + (v8 ? NK : 0u);
 }
 
 }  // namespace brc

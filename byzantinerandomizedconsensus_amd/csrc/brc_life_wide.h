@@ -24,7 +24,7 @@
 //     barrier each).  A wave with nothing to simulate or deliver still reaches each barrier.
 //
 // Scope (brc_create): sender peers, consensus protocol, BRC_MODE_REFERENCE / SPEC (one key variant) / BEB, Philox or
-// loaded proposals, constant or slow-set delays up to 8, 2-bit value ids, silent Byzantine replicas, no event log, no
+// loaded proposals, constant or slow-set delays up to 8, 2-bit value ids (3-bit: V8, below), silent Byzantine replicas, no event log, no
 // injections, a fresh engine run to completion.  Overflow (an origin's window full, more than min(Q, SENDQ_MAX)
 // SENDs of one replica in one step), step-cap stops and t_stop behave as in brc_life.h.  Results are identical to the
 // wide step kernel's (tests/test_gpu_wide_life.py checks both against the C oracle).
@@ -41,6 +41,15 @@
 // phase slot 0 of variants 0 / 1 of a Byzantine origin is ever a pattern key).  Step 1 is entered although nothing
 // may arrive then: it is the step of the pattern's second action, as in the oracle.  The PAT = false instantiations
 // compile to what they did.
+//
+// V8 (BRC_FLAG_LIFE_VALUES): 3-bit consensus value ids (seven proposal strings besides "-1"), as brc_step_wide.h's V8.
+// A slot's metadata word has no spare bit (tend 16, s + 1 14, a 2-bit id), so the 3-bit id of a slot lives in a byte
+// plane of its own, val[NK] u8 in LDS, written where the metadata is claimed and read where the consensus pass read
+// the 2-bit field.  `order` packs 3-bit fields (eight of them fill cons0_pack's 24 bits).  Host-mask planes 0..3
+// stay in LDS; planes 4..7 live in the HBM buffer P.hmask, [instance][8][NW][NPAD] u64 (the step kernel's V8 layout;
+// planes 0..3 of it are unused here), every lane its own column, touched only by a delivery that carries such an id.
+// The host zeroes the buffer before every run (clear_state).  REFERENCE and BEB only: SPEC consensus is binary.
+// The V8 = false instantiations compile to what they did.
 #pragma once
 #include "brc_life.h"
 
@@ -50,13 +59,16 @@
 
 namespace brc {
 
-template <int NPAD, int MODE, bool PAT = false>
+template <int NPAD, int MODE, bool PAT = false, bool V8 = false>
 __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const Params* __restrict__ pp) {
     const Params& P = *pp;
     constexpr bool SPEC = MODE == BRC_MODE_SPEC, BEB = MODE == BRC_MODE_BEB, CONN = false;   // (brc_life_cell.h reads all three)
     static_assert(NPAD == 128 || NPAD == 256, "wide committees: two or four waves");
     static_assert(MODE == BRC_MODE_REFERENCE || MODE == BRC_MODE_SPEC || MODE == BRC_MODE_BEB, "sender peers");
     static_assert(!PAT || MODE != BRC_MODE_SPEC, "the pattern needs two key variants: SPEC above 64 replicas has one");
+    static_assert(!V8 || MODE != BRC_MODE_SPEC, "3-bit value ids: reference / best-effort (SPEC consensus is binary)");
+    // consensus value ids: VB bits each, NVAL of them; VREP has a 1 in the low bit of every VB-bit field of `order`
+    constexpr uint32_t NVAL = V8 ? 8u : 4u, VB = V8 ? 3u : 2u, VMASK = NVAL - 1u, VREP = V8 ? 0x249249u : 0x55u;
     constexpr uint32_t KC = PAT ? 4u : 2u;           // class bitmaps per key word
     constexpr uint32_t NW = NPAD / 64;
     constexpr uint32_t RW = LIFE_RW;                 // ring rows (> the longest key lifetime, 4 Dd <= 32)
@@ -72,6 +84,7 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
     // ---- LDS carve (lds_bytes_life_wide): kab[nkw][2] u64 | consensus area (REFERENCE / BEB hm[4][NW][NPAD] u64,
     // SPEC cnt[Q][NPAD] u32) | meta[NK] u32 | rg[4][RW] u32 | ctl[16] u32 | dA[NK], dB[NK] u8 | sq[Q][NPAD] u8
     // PAT: kab[nkw][4], and after sq: pbyz[4] u64 | pcnt[8] u32 | oA[2 NPAD], oB[2 NPAD] u8
+    // V8: val[NK] u8 (the slots' 3-bit value ids) at the end
     uint64_t* const s_kab = smem;                    // the step's consumed class bitmaps per key word: class A, class B
     uint64_t* const s_hm = s_kab + KC * nkw;
     uint32_t* const s_cnt = (uint32_t*)s_hm;
@@ -88,6 +101,7 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
     uint32_t* const s_pcnt = (uint32_t*)(s_pbyz + 4);
     uint8_t* const s_oA = (uint8_t*)(s_pcnt + 8);    // PAT: out-class delivery steps of pattern key 2 b + v (as dA / dB)
     uint8_t* const s_oB = s_oA + 2 * NPAD;
+    uint8_t* const s_val = PAT ? s_oB + 2 * NPAD : s_sq + Q * NPAD;   // V8: value id of slot k (set with s_meta[k])
 
     const uint32_t d = tid;
     const uint64_t g = P.inst_offset + inst;
@@ -174,6 +188,10 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
     uint32_t clr = 0;                                // this replica's keys created this step: bit s mod Q (Q <= 32)
     auto hm = [&](uint32_t v, uint32_t w) -> uint64_t& { return s_hm[(v * NW + w) * NPAD + d]; };
     auto cnt = [&](uint32_t q) -> uint32_t& { return s_cnt[q * NPAD + d]; };
+    // V8: this lane's word w of plane v (4..7) in the HBM buffer (brc_step_wide.h ghm)
+    auto ghm = [&](uint32_t v, uint32_t w) -> gptr_t<uint64_t> {
+        return gp((uint64_t*)P.hmask) + ((inst * NVAL + v) * NW + w) * NPAD + d;
+    };
 
     // honest origin d broadcasts SEND for its key (d, s) with value v: the slot is claimed now (its own thread's
     // slots only), its lifetime is simulated after the step (brc_life.h send_key_now)
@@ -181,7 +199,12 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
         const uint32_t k = (d * NV) * Q + (s & Qm);
         const uint32_t m = s_meta[k];
         if ((lm_s1(m) != 0 && t < lm_tend(m)) || s >= 0x3FFEu) { ovf = true; return; }
-        s_meta[k] = ((t + 1u) << 16) | ((v & 3u) << 14) | (s + 1u);   // busy until simulated
+        if constexpr (V8) {
+            s_meta[k] = ((t + 1u) << 16) | (s + 1u);   // busy until simulated; the id in its own plane
+            s_val[k] = (uint8_t)v;
+        } else {
+            s_meta[k] = ((t + 1u) << 16) | ((v & 3u) << 14) | (s + 1u);   // busy until simulated
+        }
         clr |= 1u << (s & Qm);
         st_msgs += n;
         st_smax = max(st_smax, s);
@@ -193,7 +216,7 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
     auto send_key = [&](uint32_t s, uint32_t v) {
         if (defer) {
             if (sq_n == 0) sq_s = s;
-            if (s == sq_s + sq_n && sq_n < Q && sq_n < SENDQ_MAX) s_sq[sq_n++ * NPAD + d] = (uint8_t)(v & 3u);
+            if (s == sq_s + sq_n && sq_n < Q && sq_n < SENDQ_MAX) s_sq[sq_n++ * NPAD + d] = (uint8_t)(v & VMASK);
             else ovf = true;                         // a (Q+1)-th would find its slot busy (brc_step_wide.h send_later)
             return;
         }
@@ -203,26 +226,51 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
         for (uint32_t i = 0; i < sq_n; ++i) send_key_now(sq_s + i, s_sq[i * NPAD + d]);
         sq_n = 0;
     };
+    auto popc_hm = [&](uint32_t v) -> uint32_t {
+        uint32_t c = 0;
+        if constexpr (V8) {
+            if (v >= 4) {
+                for (uint32_t w = 0; w < NW; ++w) c += (uint32_t)__popcll(*ghm(v, w));
+                return c;
+            }
+        }
+        for (uint32_t w = 0; w < NW; ++w) c += (uint32_t)__popcll(hm(v, w));
+        return c;
+    };
     auto get_max_val = [&](uint32_t bound2) -> uint32_t {          // :64-68
         for (uint32_t i = 0; i < nvals; ++i) {
-            const uint32_t v = (order >> (2 * i)) & 3;
-            uint32_t c = 0;
-            for (uint32_t w = 0; w < NW; ++w) c += (uint32_t)__popcll(hm(v, w));
-            if (2 * c > bound2) return v;
+            const uint32_t v = (order >> (VB * i)) & VMASK;
+            if (2 * popc_hm(v) > bound2) return v;
         }
         return 0;                                                    // str(NONE) == "-1"
     };
     auto cons_reset = [&]() {
+        if constexpr (V8) {
+            // the HBM planes in use are the ids above 3 in `order` (a plane is non-zero only after an insertion)
+            for (uint32_t i = 0; i < nvals; ++i) {
+                const uint32_t v = (order >> (VB * i)) & VMASK;
+                if (v >= 4)
+                    for (uint32_t w = 0; w < NW; ++w) *ghm(v, w) = 0;
+            }
+        }
         vcount = 0; nvals = 0; order = 0;
         for (uint32_t v = 0; v < 4; ++v)
             for (uint32_t w = 0; w < NW; ++w) hm(v, w) = 0;
     };
     auto cons_deliver_vh = [&](uint32_t v, uint32_t host) {          // :53-106
-        const uint32_t x = order ^ (v * 0x55u);
-        const uint32_t valid = (1u << (2 * nvals)) - 1u;
-        const bool found = (~(x | (x >> 1)) & 0x55u & valid) != 0;
-        if (!found) { order |= v << (2 * nvals); ++nvals; }         // :57-58
-        hm(v, host >> 6) |= 1ull << (host & 63);                    // :60
+        // v already inserted? every VB-bit field of `order` compared at once (nvals <= NVAL)
+        const uint32_t x = order ^ (v * VREP);
+        const uint32_t valid = (1u << (VB * nvals)) - 1u;
+        bool found;
+        if constexpr (V8) found = (~(x | (x >> 1) | (x >> 2)) & VREP & valid) != 0;
+        else found = (~(x | (x >> 1)) & VREP & valid) != 0;
+        if (!found) { order |= v << (VB * nvals); ++nvals; }        // :57-58
+        if constexpr (V8) {
+            if (v >= 4) *ghm(v, host >> 6) |= 1ull << (host & 63);
+            else hm(v, host >> 6) |= 1ull << (host & 63);
+        } else {
+            hm(v, host >> 6) |= 1ull << (host & 63);                 // :60
+        }
         ++vcount;                                                    // :61
         if (vcount >= P.T_cnt && phase == 1) {                       // :71
             const uint32_t prop = get_max_val(P.bound_p1);           // :73
@@ -410,7 +458,7 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
         const uint32_t v = (P.proposals == BRC_PROPOSALS_PHILOX) ? proposal_id(P.seed, g, d)
                                                                  : (uint32_t)gp(P.prop)[inst * n + d];
         round = 1; phase = 1;
-        send_key(0, v & 3);
+        send_key(0, v & VMASK);
         if constexpr (SPEC) spec_advance();
     }
     if (block_or(ovf ? 1u : 0u)) {
@@ -430,7 +478,12 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
                 // ECHO and READY, stamped 1, at 2 or 1 + Dd
                 uint32_t pend = 0;
                 if (has) {
-                    s_meta[k] = (1u << 16) | ((1u + v) << 14) | 1u;
+                    if constexpr (V8) {
+                        s_meta[k] = (1u << 16) | 1u;
+                        s_val[k] = (uint8_t)(1u + v);
+                    } else {
+                        s_meta[k] = (1u << 16) | ((1u + v) << 14) | 1u;
+                    }
                     st_msgs += v ? n / 2u : (n + 1u) / 2u;          // the SEND, to every replica of parity v
                     pend = (1u << (Dd - 1u)) | (1u << (10u + Dd)) | (1u << (20u + Dd));
                     if (oF) pend |= 1u | (1u << 11) | (1u << 21);
@@ -613,6 +666,7 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
                     bits &= ~(1ull << best);
                     const uint32_t k = w * 64 + best;
                     if constexpr (SPEC) spec_deliver(k);
+                    else if constexpr (V8) cons_deliver_vh(s_val[k], k >> ksh);
                     else cons_deliver_vh((s_meta[k] & 0xFFFFu) >> 14, k >> ksh);
                 }
             }
@@ -664,9 +718,9 @@ __global__ __launch_bounds__(NPAD, BRC_LIFE_WIDE_WAVES) void brc_life_wide(const
     }
 }
 
-template <int NPAD, int MODE, bool PAT = false>
+template <int NPAD, int MODE, bool PAT = false, bool V8 = false>
 int launch_life_wide_one(uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P) {
-    auto kern = brc_life_wide<NPAD, MODE, PAT>;
+    auto kern = brc_life_wide<NPAD, MODE, PAT, V8>;
     if (lds > 64 * 1024 &&
         hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return BRC_E_HIP;
@@ -687,6 +741,18 @@ template <int NPAD>
 int launch_life_wide_pat_npad(int mode, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P) {
     if (mode == BRC_MODE_BEB) return launch_life_wide_one<NPAD, BRC_MODE_BEB, true>(blocks, lds, s, P);
     if (mode == BRC_MODE_REFERENCE) return launch_life_wide_one<NPAD, BRC_MODE_REFERENCE, true>(blocks, lds, s, P);
+    return BRC_E_INVALID;
+}
+
+// the V8 instantiations (BRC_FLAG_LIFE_VALUES: 3-bit value ids): REFERENCE / BEB, with and without the pattern
+template <int NPAD>
+int launch_life_wide_val_npad(int mode, bool pat, uint32_t blocks, uint32_t lds, hipStream_t s, const Params* P) {
+    if (mode == BRC_MODE_BEB)
+        return pat ? launch_life_wide_one<NPAD, BRC_MODE_BEB, true, true>(blocks, lds, s, P)
+                   : launch_life_wide_one<NPAD, BRC_MODE_BEB, false, true>(blocks, lds, s, P);
+    if (mode == BRC_MODE_REFERENCE)
+        return pat ? launch_life_wide_one<NPAD, BRC_MODE_REFERENCE, true, true>(blocks, lds, s, P)
+                   : launch_life_wide_one<NPAD, BRC_MODE_REFERENCE, false, true>(blocks, lds, s, P);
     return BRC_E_INVALID;
 }
 

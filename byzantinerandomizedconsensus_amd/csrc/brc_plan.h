@@ -9,6 +9,7 @@
 #include <string>
 
 #include "brc_layout.h"
+#include "brc_plan_lv.h"
 
 namespace brc {
 
@@ -40,6 +41,7 @@ struct Plan {
     uint64_t nitems = 0;
     bool life_cfg = false;                       // a fresh run to completion launches the key-lifetime kernel (brc_life.h)
     bool life_pl = false, life_pat = false;      // ... in its per-link delay form; the wide kernel's pattern form
+    bool life_val = false;                       // ... the wide kernel's 3-bit value ids (BRC_FLAG_LIFE_VALUES; V8)
     uint32_t life_rw = LIFE_RW, life_lds = 0;    // ... its delivery-ring rows (LIFE_RW16 for delays above 8) and LDS bytes
     // false: the step kernel cannot serve this engine (its state would not fit, a lean key window above 32, or
     // BRC_FLAG_WIDE_LIFE): only the key-lifetime kernel runs, and the step kernel's key-slot arrays are not allocated
@@ -83,6 +85,8 @@ inline int make_plan(const brc_config& c, const PlanEnv& env, Plan* out, std::st
                                                    : nullptr;
         if (why) return refuse(why);
     }
+    // BRC_FLAG_LIFE_VALUES (brc_plan_lv.h): likewise
+    if ((why = life_values_why(c)) != nullptr) return refuse(why);
     // every fault bound 0 .. n - 1 runs (the kernels compute n - f unsigned); f = n would leave no replica to count.
     // Named here, for a committee size in range; the range check below keeps its own f >= n
     if (c.n >= 1 && c.n <= 256 && c.f >= c.n)
@@ -106,7 +110,8 @@ inline int make_plan(const brc_config& c, const PlanEnv& env, Plan* out, std::st
         (c.byz_pattern != BRC_BYZ_NONE && c.byz_pattern != BRC_BYZ_EQUIVOCATE) ||
         c.proposals > BRC_PROPOSALS_LOADED || c.mode > BRC_MODE_BEB ||
         (c.flags & ~(uint32_t)(BRC_FLAG_GENERAL_KEYS | BRC_FLAG_WIDE_RECORDS | BRC_FLAG_WIDE_VALUES |
-                               BRC_FLAG_WIDE_WINDOWS | BRC_FLAG_WIDE_LIFE | BRC_FLAG_LIFE_PATTERN)) ||
+                               BRC_FLAG_WIDE_WINDOWS | BRC_FLAG_WIDE_LIFE | BRC_FLAG_LIFE_PATTERN |
+                               BRC_FLAG_LIFE_VALUES)) ||
         // the general form at NPAD = 64 with sender peers is the reference protocol's (KMODE_XREF)
         ((c.flags & BRC_FLAG_GENERAL_KEYS) && c.n > 32 && c.n <= 64 && c.peer_mode == BRC_PEER_SENDER &&
          c.mode != BRC_MODE_REFERENCE) ||
@@ -254,10 +259,18 @@ inline int make_plan(const brc_config& c, const PlanEnv& env, Plan* out, std::st
         p.life_pl = false;
         p.life_rw = LIFE_RW;
         p.life_pat = (c.flags & BRC_FLAG_LIFE_PATTERN) != 0;
-        p.life_lds = lds_bytes_life_wide(p.npad, p.NK, p.nkw, spec, c.key_window, p.life_pat);
+        p.life_val = (c.flags & BRC_FLAG_LIFE_VALUES) != 0;
+        p.life_lds = lds_bytes_life_wide(p.npad, p.NK, p.nkw, spec, c.key_window, p.life_pat, p.life_val);
         p.life_cfg = true;
         p.step_ok = false;
         p.cons_bytes = 0;                               // the host masks / phase counters live in LDS for the whole run
+        if (p.life_val) {
+            // 3-bit value ids: host-mask planes 4..7 live in HBM, in the wide step kernel's eight-plane layout (planes
+            // 0..3 of the buffer are allocated and unused: one index formula for both kernels); wide_val / wide_rec
+            // stay false, they select step-kernel launchers
+            p.nval = 8;
+            p.cons_bytes = cons_bytes_per_item(false, true, p.lpi, p.msize, c.key_window, c.variants, p.nval);
+        }
         if (p.life_lds > 160 * 1024)
             return refuse("BRC_FLAG_WIDE_LIFE: key_window * variants = " + std::to_string(c.key_window * c.variants) +
                           " exceeds the wide key-lifetime kernel's LDS (lds " + std::to_string(p.life_lds) + " B of 163840)");

@@ -29,7 +29,7 @@ class Engine:
                  proposals=L.PROPOSALS_NONE, byz_pattern=L.BYZ_NONE, byzantine=(), event_capacity=0,
                  instance_offset=0, device=0, mode=L.MODE_REFERENCE, coin_seed=0, peer_mode=L.PEER_SENDER,
                  general_keys=False, wide_records=False, wide_values=False, wide_windows=False, wide_life=False,
-                 life_pattern=False):
+                 life_pattern=False, life_values=False):
         self._lib = L.load()
         self._h = ctypes.c_void_p()
         mask = 0
@@ -44,7 +44,8 @@ class Engine:
                             byzantine_mask=mask & M64, device=device, mode=mode, coin_seed=coin_seed,
                             flags=(L.FLAG_GENERAL_KEYS if general_keys else 0) | (L.FLAG_WIDE_RECORDS if wide_records else 0) |
                             (L.FLAG_WIDE_VALUES if wide_values else 0) | (L.FLAG_WIDE_WINDOWS if wide_windows else 0) |
-                            (L.FLAG_WIDE_LIFE if wide_life else 0) | (L.FLAG_LIFE_PATTERN if life_pattern else 0))
+                            (L.FLAG_WIDE_LIFE if wide_life else 0) | (L.FLAG_LIFE_PATTERN if life_pattern else 0) |
+                            (L.FLAG_LIFE_VALUES if life_values else 0))
         for w in range(3):
             self.cfg.byzantine_mask_hi[w] = (mask >> (64 * (w + 1))) & M64
         rc = self._lib.brc_create(ctypes.byref(self.cfg), ctypes.byref(self._h))

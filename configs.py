@@ -141,6 +141,11 @@ def workloads(L):
     W["cfg5-ref-slow-eq"] = (6144, True, dict(W["cfg5-ref-slow"][2], key_window=4, variants=2,
                                               byz_pattern=L.BYZ_EQUIVOCATE, byzantine=list(range(171, 256))))
     W["cfg5-ref-slow-eq-life"] = (6144, True, dict(W["cfg5-ref-slow-eq"][2], wide_life=True, life_pattern=True))
+    # the -life rows with BRC_FLAG_LIFE_VALUES and the same binary proposals: what opting in to three-bit value ids costs
+    # on the wide key-lifetime kernel (a value byte per slot in LDS, 3-bit `order` fields, host-mask planes 4..7 left in
+    # HBM untouched); informational, against their -life twins and the step kernel's -wval row
+    for name in ("cfg5-ref-slow", "cfg5-ref-slow-q16"):
+        W[name + "-life-v8"] = (W[name + "-life"][0], True, dict(W[name + "-life"][2], life_values=True))
     return W
 
 

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define BRC_ABI_VERSION 12
+#define BRC_ABI_VERSION 13
 
 enum {
     BRC_OK = 0,
@@ -185,9 +185,26 @@ typedef struct {
  * on anything else fails brc_create with BRC_E_INVALID and a reason naming it: without BRC_FLAG_WIDE_LIFE, n <= 64 (a
  * pattern there runs on the step kernel, as it does at n in 33..64 whatever the flags), connection peers,
  * BRC_MODE_SPEC (variants = 1 above 64 replicas), byz_pattern = BRC_BYZ_NONE, variants = 1.  Without the flag nothing
- * changes: BRC_FLAG_WIDE_LIFE with a pattern is still refused. */
+ * changes: BRC_FLAG_WIDE_LIFE with a pattern is still refused.
+ * BRC_FLAG_LIFE_VALUES (v13; bit 64 is unassigned and refused): together with BRC_FLAG_WIDE_LIFE, the wide key-lifetime
+ * kernel keeps 3-bit consensus value ids (csrc/brc_life_wide.h V8): brc_load_proposals accepts ids 0..7 (seven proposal
+ * strings besides "-1") and the run stays on the lifetime kernel; Philox proposals stay binary; decisions are read with
+ * brc_read_value_decisions (brc_read_decisions: BRC_E_STATE once an id >= 4 was decided).  Results are those of a
+ * BRC_FLAG_WIDE_VALUES engine on the wide step kernel, field for field; with binary proposals those of the
+ * BRC_FLAG_WIDE_LIFE engine without the flag.  May be combined with BRC_FLAG_WIDE_WINDOWS and BRC_FLAG_LIFE_PATTERN
+ * (the pattern's ids stay 1 and 2).  Eligible: everything BRC_FLAG_WIDE_LIFE requires, BRC_MODE_REFERENCE or
+ * BRC_MODE_BEB.  One workgroup's LDS is BRC_FLAG_WIDE_LIFE's (or the pattern form's) plus one byte per key slot, the
+ * slot's value id: + 1 / 2 / 4 KB at NPAD 128 and + 2 / 4 / 8 KB at NPAD 256 for key_window * variants = 8 / 16 / 32
+ * (the largest carve: 100,928 B at NPAD 256, window 32).  Host-mask planes 0..3 stay in LDS; planes 4..7 live in device
+ * memory, in a buffer of the wide step kernel's layout [instance][8][NPAD / 64][NPAD] u64 -- all eight planes are
+ * allocated, NPAD^2 B per instance (16 KB at NPAD 128, 64 KB at NPAD 256), of which the kernel touches the upper half,
+ * and only on a delivery that carries an id >= 4; brc_create, brc_reset and brc_reset_at zero it.  The flag set on
+ * anything else fails brc_create with BRC_E_INVALID and a reason naming it: without BRC_FLAG_WIDE_LIFE, n <= 64,
+ * connection peers, BRC_MODE_SPEC (its consensus is binary); with BRC_FLAG_WIDE_RECORDS / BRC_FLAG_WIDE_VALUES it is
+ * refused as BRC_FLAG_WIDE_LIFE refuses them.  Without the flag nothing changes: a BRC_FLAG_WIDE_LIFE engine still
+ * refuses id 4. */
 enum { BRC_FLAG_GENERAL_KEYS = 1, BRC_FLAG_WIDE_RECORDS = 2, BRC_FLAG_WIDE_VALUES = 4, BRC_FLAG_WIDE_WINDOWS = 8,
-       BRC_FLAG_WIDE_LIFE = 16, BRC_FLAG_LIFE_PATTERN = 32 };
+       BRC_FLAG_WIDE_LIFE = 16, BRC_FLAG_LIFE_PATTERN = 32, BRC_FLAG_LIFE_VALUES = 128 };
 
 /* Injections may arrive between brc_run calls.  A record's time must not lie before the step its instance's wave
  * item stands at (brc_instance_result.t_now once the engine has run): t < t_now is BRC_E_STATE.  t == t_now is
