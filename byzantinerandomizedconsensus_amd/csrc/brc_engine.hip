@@ -15,12 +15,11 @@
 #include <string.h>
 
 #include <algorithm>
-#include <map>
 #include <string>
 #include <vector>
-#include <unordered_map>
 
 #include "brc_internal.h"
+#include "brc_inject.h"
 #include "brc_plan.h"
 
 namespace {
@@ -167,37 +166,7 @@ struct Engine : Plan {
     Params hparams;
     std::vector<std::vector<InjDev>> pending;   // per item: uploaded-but-unconsumed + new
     bool inj_dirty = false, pattern_active = false;
-    // slot generation budget: the allocations of one key slot in an epoch (brc_reset to brc_reset) are bounded
-    // by gen_used() below; gen_base sums the epochs since the last full clear
-    uint64_t gen_base = 0, gen_cur = 0;
-    // what bounds them (tagged kernels only; DESIGN.md section 3, "Key slots"), per epoch:
-    // gen_smax: the largest phase index a launch has reported; gen_extra: over the key slots, the most injected
-    // KEY / SEND records that can allocate one slot beyond one per key (under the consensus protocol every such
-    // record: the kernel may allocate the key itself); gen_passes: the most PROPOSE records of one replica (each
-    // starts its phase indices over), plus one when the engine proposes by itself
-    uint64_t gen_smax = 0, gen_extra = 0, gen_props = 0;
-    std::unordered_map<uint64_t, uint32_t> key_recs;    // instance << 32 | kp << 16 | s -> allocating records
-    std::unordered_map<uint64_t, uint32_t> slot_extra;  // instance << 32 | slot -> the slot's count for gen_extra
-    std::unordered_map<uint64_t, uint32_t> prop_recs;   // instance << 32 | node -> PROPOSE records
-    // injected SENDs per key (instance << 32 | kp << 16 | s): how many, and each sender's destinations (all four
-    // words: the wide kernels' extra SENDs drop a node's used links over bw words)
-    struct SendDst { uint32_t node; uint64_t dst[4]; };
-    std::unordered_map<uint64_t, uint32_t> send_count;
-    std::unordered_map<uint64_t, std::vector<SendDst>> send_dst;
-    // type: 0 = an extra SEND; BRC_ECHO / BRC_READY = a Byzantine replica's message to a subset of the peers
-    struct XRec { uint32_t k, t, seg, type; uint64_t smask, dst; };
-    std::unordered_map<uint64_t, std::vector<XRec>> xrec;   // item -> records in flight (P.xsend)
-    // injected ECHO / READY of Byzantine replicas on the non-lean narrow kernels with sender peers, per
-    // msg_key(instance, node, type, kp, s): the links used so far, and whether some of them went through a record
-    // (the sending lane's cell then keeps no send step, and a later broadcast becomes a record too)
-    std::unordered_map<uint64_t, uint64_t> msg_used;
-    std::unordered_map<uint64_t, bool> msg_rec;
-    // the same on the wide kernels under BRC_FLAG_WIDE_RECORDS (brc_step_wide.h REC): one instance per item, one
-    // sender per record, destination and used-link sets of bw words (four kept).  type 0: an extra SEND
-    struct WRec { uint32_t k, t, type, node; uint64_t dst[4]; };
-    struct WUsed { uint64_t w[4] = {0, 0, 0, 0}; bool rec = false; };
-    std::unordered_map<uint64_t, std::vector<WRec>> wrec;   // instance -> records in flight (P.xsend)
-    std::map<std::pair<uint64_t, uint64_t>, WUsed> wmsg;    // (instance, wmsg_key) -> links used, had a record
+    InjectBook book;                            // the injections taken, the slot generation budget (brc_inject.h)
     std::vector<uint64_t> hbyz;                 // host copy of the per-instance Byzantine masks [instance][bw]
     // key-lifetime kernel (brc_life.h; life_cfg: eligible configuration): engine fresh since create / reset,
     // and whether the last run used it (its instances are then final: no re-opening injections)
@@ -216,34 +185,6 @@ thread_local std::string g_create_err;    // brc_last_error(NULL): the last brc_
             return BRC_E_HIP;                                                          \
         }                                                                              \
     } while (0)
-
-// bits of replicas 64w .. 64w+63 that exist in an n-replica instance
-static uint64_t word_mask(uint32_t n, uint32_t w) {
-    const uint32_t lo = 64 * w;
-    return n >= lo + 64 ? ~0ull : (n <= lo ? 0ull : ((1ull << (n - lo)) - 1));
-}
-
-// (instance, node, type, key) of an injected ECHO / READY at n <= 64: node < 64, kp < 256, s < 2^16
-static uint64_t msg_key(uint64_t instance, uint32_t node, uint32_t type, uint32_t kp, uint32_t s) {
-    return (instance << 32) | ((uint64_t)node << 26) | ((uint64_t)(type == BRC_READY) << 25) | ((uint64_t)kp << 16) | s;
-}
-
-// (node, type, key) of an injected ECHO / READY at n > 64: node < 256, kp < 1024, s < 2^16
-static uint64_t wmsg_key(uint32_t node, uint32_t type, uint32_t kp, uint32_t s) {
-    return ((uint64_t)node << 40) | ((uint64_t)(type == BRC_READY) << 32) | ((uint64_t)kp << 16) | s;
-}
-
-// Slot generations (tagged kernels): how far this epoch can have advanced the tag of one key slot, plus one to
-// spare.  The kernels allocate a slot (gen + 1, brc_step.h) in send_key_now -- a replica's own key of phase index
-// s, once per s and pass, s rising within a pass (a PROPOSE starts the next pass) -- and in send_rec, for every
-// KEY record and every SEND record whose key is not declared-and-unsent.  With one record per key the records are
-// the keys of the slot, at most smax / Q + 1 of them; every further record is counted in gen_extra.
-static uint64_t gen_passes(const Engine* e) {
-    return std::max<uint64_t>(1, e->gen_props + (e->cfg.proposals != BRC_PROPOSALS_NONE ? 1u : 0u));
-}
-static uint64_t gen_used(const Engine* e) {
-    return gen_passes(e) * (e->gen_smax / e->cfg.key_window + 1) + e->gen_extra + 1;
-}
 
 // The one place a kernel is chosen: the plan's family and this run's `life` decision (brc_run)
 static int launch_kernel(const Engine* e, bool life, const Params* P) {
@@ -328,8 +269,7 @@ static int clear_state(Engine* e, bool full) {
         }
         HIPCHK(e, hipMemsetAsync(e->meta, 0, e->meta_bytes, e->stream));
         HIPCHK(e, hipMemsetAsync(e->mgen, 0, e->mgen_bytes, e->stream));
-        e->gen_base = 0;
-        e->gen_cur = 0;
+        e->book.full_clear();
     } else {
         hipLaunchKernelGGL(reset_slots, dim3((uint32_t)((e->keys + 255) / 256)), dim3(256), 0, e->stream, e->meta, e->mgen,
                            e->keys);
@@ -532,305 +472,32 @@ int brc_load_byzantine(void* h, const uint64_t* masks) {
     return BRC_OK;
 }
 
+// Everything brc_inject decides is stage_injections' (brc_inject.h); what is left is the device's part
 int brc_inject(void* h, const brc_injection* list, size_t count) {
     Engine* e = static_cast<Engine*>(h);
     if (!e || (!list && count)) return BRC_E_INVALID;
-    if (e->pattern_active) { e->err = "explicit injections cannot be combined with byz_pattern"; return BRC_E_STATE; }
-    const brc_config& c = e->cfg;
-    if (!e->step_ok && count) { e->err = life_only_why(*e, false); return BRC_E_UNSUPPORTED; }
-    const uint64_t all = (c.n >= 64) ? ~0ull : ((1ull << c.n) - 1);
-    std::vector<ItemState> its;
-    std::vector<InstState> ist;
-    bool have_state = false;
-    std::vector<uint64_t> reopen;
-    std::vector<InjDev> staged;
-    std::vector<uint64_t> staged_item;
-    std::unordered_map<uint64_t, uint32_t> new_count;                                   // this batch's SENDs
-    std::unordered_map<uint64_t, std::vector<Engine::SendDst>> new_dst;
-    std::unordered_map<uint64_t, uint64_t> new_used;                                    // this batch's ECHO / READY links
-    std::unordered_map<uint64_t, bool> new_rec;
-    // restricted ECHO / READY: the non-lean narrow step kernels with sender peers (brc_step.h record pre-pass)
-    const bool msg_records = !e->wide && !e->compact && c.peer_mode == BRC_PEER_SENDER;
-    // ... and the wide kernels of an engine created with BRC_FLAG_WIDE_RECORDS (sender peers: brc_create)
-    std::map<std::pair<uint64_t, uint64_t>, Engine::WUsed> new_wmsg;
-    auto any4 = [](const uint64_t* w) { return (w[0] | w[1] | w[2] | w[3]) != 0; };
-    for (size_t i = 0; i < count; ++i) {
-        const brc_injection& x = list[i];
-        if (x.instance >= c.instances || x.node >= c.n || x.t > c.step_cap) { e->err = "injection out of range"; return BRC_E_INVALID; }
-        if (x.value < 0 || x.value >= (int)(c.mode == BRC_MODE_SPEC ? 4u : e->nval) || x.s >= 0xFFFE) {
-            e->err = "value id / phase index out of range (value ids 4..7 need n <= 32, connection peers up to n = 64, "
-                     "BRC_FLAG_GENERAL_KEYS at n in 33..64 or BRC_FLAG_WIDE_VALUES at n > 64 with sender peers; not SPEC)";
-            return BRC_E_INVALID;
-        }
-        bool drop = false;                       // a repeated SEND carried on no link (sender peers)
-        InjDev r = {};
-        r.t = x.t; r.kind = (uint8_t)x.kind; r.type = (uint8_t)x.type; r.node = (uint8_t)x.node;
-        r.seg = (uint8_t)(x.instance % e->ipw); r.value = (int8_t)x.value; r.s = (uint16_t)x.s;
-        r.dst = x.dst_mask & all;
-        bool full = (r.dst == word_mask(c.n, 0));
-        for (uint32_t w = 1; w < e->bw; ++w) {
-            r.dst_hi[w - 1] = x.dst_mask_hi[w - 1] & word_mask(c.n, w);
-            full = full && r.dst_hi[w - 1] == word_mask(c.n, w);
-        }
-        r.restricted = (x.kind == BRC_INJ_SEND && !full) ? 1 : 0;
-        if (x.kind == BRC_INJ_PROPOSE) {
-            if (c.protocol != BRC_PROTO_CONSENSUS) { e->err = "PROPOSE needs the consensus protocol"; return BRC_E_INVALID; }
-        } else if (x.kind == BRC_INJ_DELIVER) {
-            if (c.protocol != BRC_PROTO_CONSENSUS) { e->err = "DELIVER needs the consensus protocol"; return BRC_E_INVALID; }
-            if (c.mode == BRC_MODE_SPEC) { e->err = "DELIVER: SPEC consensus counts phase-indexed keys"; return BRC_E_UNSUPPORTED; }
-            if (x.kp >= c.n) { e->err = "DELIVER host out of range"; return BRC_E_INVALID; }
-            r.slot = (uint16_t)x.kp;               // the message's host
-        } else if (x.kind == BRC_INJ_SEND || x.kind == BRC_INJ_MSG || x.kind == BRC_INJ_KEY) {
-            if (x.kp >= c.n * c.variants) { e->err = "kp out of range"; return BRC_E_INVALID; }
-            r.slot = (uint16_t)(x.kp * c.key_window + (x.s % c.key_window));
-            if (x.kind == BRC_INJ_MSG) {
-                if (x.type != BRC_ECHO && x.type != BRC_READY) { e->err = "MSG type must be ECHO or READY"; return BRC_E_INVALID; }
-                if (!full && !msg_records && !e->wide_rec) {
-                    e->err = c.peer_mode == BRC_PEER_CONNECTION
-                        ? "an ECHO / READY to a subset of the peers: not with connection peers (every message is a new "
-                          "peer there; the record pre-pass counts senders)"
-                        : e->wide ? "an ECHO / READY to a subset of the peers: not on the wide kernels (n > 64), whose "
-                                    "receivers ballot over the senders' cells"
-                                  : "an ECHO / READY to a subset of the peers: not on the lean kernels (n in 33..64 with "
-                                    "sender peers; BRC_FLAG_GENERAL_KEYS runs the general form)";
-                    return BRC_E_UNSUPPORTED;
-                }
-                const bool byz = (e->hbyz[x.instance * e->bw + x.node / 64] >> (x.node % 64)) & 1ull;
-                if (!full && !byz) {
-                    e->err = "an ECHO / READY to a subset of the peers needs a Byzantine sender: an honest replica's own "
-                             "later broadcast would need per-link suppression the cells do not have";
-                    return BRC_E_UNSUPPORTED;
-                }
-                if (msg_records && byz) {
-                    // the links (node, type, key) used before, this batch included.  A message to a subset, and every
-                    // later one of a (node, type, key) that had one, goes over the remaining links as a record of the
-                    // item's table (possibly over none: it still is an action of its step); a broadcast to every peer
-                    // with no record before it keeps the cell path, which uses every link
-                    const uint64_t m64 = msg_key(x.instance, x.node, x.type, x.kp, x.s);
-                    uint64_t used = 0;
-                    bool rec = false;
-                    for (const auto* mp : {&e->msg_used, &new_used}) {
-                        auto it = mp->find(m64);
-                        if (it != mp->end()) used |= it->second;
-                    }
-                    for (const auto* mp : {&e->msg_rec, &new_rec}) rec = rec || mp->count(m64);
-                    if (!full || rec) {
-                        r.dst &= ~used;
-                        r.restricted = (uint8_t)(1u | ((used == 0 && r.dst != 0) ? 2u : 0u));   // bit 1: a SEND event
-                        new_rec[m64] = true;
-                    }
-                    new_used[m64] |= r.dst;
-                }
-                if (e->wide_rec && byz) {
-                    // the same over bw destination words (the words past bw stay zero)
-                    const auto wk = std::make_pair((uint64_t)x.instance, wmsg_key(x.node, x.type, x.kp, x.s));
-                    Engine::WUsed u;
-                    for (const auto* mp : {&e->wmsg, &new_wmsg}) {
-                        auto it = mp->find(wk);
-                        if (it == mp->end()) continue;
-                        for (int w = 0; w < 4; ++w) u.w[w] |= it->second.w[w];
-                        u.rec = u.rec || it->second.rec;
-                    }
-                    uint64_t* dw[4] = {&r.dst, &r.dst_hi[0], &r.dst_hi[1], &r.dst_hi[2]};
-                    if (!full || u.rec) {
-                        const bool first = !any4(u.w);
-                        for (int w = 0; w < 4; ++w) *dw[w] &= ~u.w[w];
-                        const uint64_t left[4] = {*dw[0], *dw[1], *dw[2], *dw[3]};
-                        r.restricted = (uint8_t)(1u | ((first && any4(left)) ? 2u : 0u));   // bit 1: a SEND event
-                        u.rec = true;
-                    }
-                    for (int w = 0; w < 4; ++w) u.w[w] |= *dw[w];
-                    new_wmsg[wk] = u;
-                }
-            } else if (x.kind == BRC_INJ_SEND) {
-                // a second SEND of a key (another origin or the same, one payload string SENT again):
-                // an extra-SEND record on the non-lean narrow step kernels and on the wide kernels of an engine
-                // created with BRC_FLAG_WIDE_RECORDS; the lean and the flagless wide kernels model one SEND per key
-                const uint64_t k64 = (x.instance << 32) | (uint64_t)(x.kp * 0x10000u + x.s);
-                auto it0 = e->send_count.find(k64);
-                auto it1 = new_count.find(k64);
-                const uint32_t before = (it0 != e->send_count.end() ? it0->second : 0u) +
-                                        (it1 != new_count.end() ? it1->second : 0u);
-                const bool one_send = e->compact || (e->wide && !e->wide_rec);
-                if (one_send && before) {
-                    e->err = "a key can be SENT only once on this kernel (n in 33..64 with sender peers, or n > 64 "
-                             "without BRC_FLAG_WIDE_RECORDS)";
-                    return BRC_E_UNSUPPORTED;
-                }
-                ++new_count[k64];
-                // this node's earlier SENDs of the key (this batch included): r.type = 1 marks a repeat
-                // (brc_step.h: a COPY event with connection peers); sender peers carry a repeated
-                // message on a link no further (the links it used are dropped from the record)
-                uint64_t prev[4] = {0, 0, 0, 0};
-                bool had = false;
-                for (const auto* mp : {&e->send_dst, &new_dst}) {
-                    auto it = mp->find(k64);
-                    if (it != mp->end())
-                        for (const auto& q : it->second)
-                            if (q.node == x.node) {
-                                for (int w = 0; w < 4; ++w) prev[w] |= q.dst[w];
-                                had = true;
-                            }
-                }
-                new_dst[k64].push_back(Engine::SendDst{x.node, {r.dst, r.dst_hi[0], r.dst_hi[1], r.dst_hi[2]}});
-                // a key SENT before (by any node): an extra-SEND record (bit 1), bit 0 = this node's repeat
-                const bool again = !one_send && before > 0;
-                r.type = (again ? 2 : 0) | (had ? 1 : 0);
-                if (c.peer_mode == BRC_PEER_SENDER) {
-                    r.dst &= ~prev[0];
-                    for (int w = 0; w < 3; ++w) r.dst_hi[w] &= ~prev[w + 1];
-                }
-                drop = had && !(r.dst | r.dst_hi[0] | r.dst_hi[1] | r.dst_hi[2]);
-            }
-        } else {
-            e->err = "unknown injection kind";
-            return BRC_E_INVALID;
-        }
-        if (!have_state) {
-            its.resize(e->nitems); ist.resize(c.instances);
-            HIPCHK(e, hipMemcpyAsync(its.data(), e->items, e->nitems * sizeof(ItemState), hipMemcpyDeviceToHost, e->stream));
-            HIPCHK(e, hipMemcpyAsync(ist.data(), e->inst, c.instances * sizeof(InstState), hipMemcpyDeviceToHost, e->stream));
-            HIPCHK(e, hipStreamSynchronize(e->stream));
-            have_state = true;
-        }
-        const uint64_t item = x.instance / e->ipw;
-        if (its[item].initialized != 0 && x.t < its[item].t) { e->err = "injection time is before the instance's current step"; return BRC_E_STATE; }
-        if (ist[x.instance].status == BRC_QUIESCENT && e->life_done) {
-            e->err = "instance finished by the key-lifetime kernel (no step state to resume): brc_reset first";
-            return BRC_E_STATE;
-        }
-        if (ist[x.instance].status != BRC_QUIESCENT && ist[x.instance].status != BRC_RUNNING) {
-            e->err = "instance already stopped"; return BRC_E_STATE;
-        }
-        // a repeated SEND carried on no link (sender peers) changes no instance state: accepted, not staged
-        // (after the stopped-instance checks: a stopped instance refuses it like every other injection)
-        if (drop) continue;
-        if (ist[x.instance].status == BRC_QUIESCENT) reopen.push_back(x.instance);
-        staged.push_back(r);
-        staged_item.push_back(item);
+    auto fetch = [e](std::vector<ItemState>& its, std::vector<InstState>& ist) -> int {
+        its.resize(e->nitems); ist.resize(e->cfg.instances);
+        HIPCHK(e, hipMemcpyAsync(its.data(), e->items, e->nitems * sizeof(ItemState), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(e, hipMemcpyAsync(ist.data(), e->inst, e->cfg.instances * sizeof(InstState), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        return BRC_OK;
+    };
+    InjectBatch b;
+    const int rc = stage_injections(*e, e->cfg, e->book, e->hbyz, e->pattern_active, e->life_done, list, count, fetch, &b,
+                                    &e->err);
+    if (rc) return rc;
+    const size_t words = (e->wide_rec ? WREC_W : 3) * XSEND_MAX;
+    for (const auto& tb : b.tables) {
+        HIPCHK(e, hipMemcpyAsync(e->xsend + tb.item * words, tb.words.data(), words * 8, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(e, hipMemcpyAsync(e->xsn + tb.item, &tb.count, 4, hipMemcpyHostToDevice, e->stream));
     }
-    // extra-SEND records (r.type bit 1) and restricted ECHO / READY records (r.restricted) into their items'
-    // tables: a record of the same key, step, type and destinations without this sender takes it, else a new one (records whose arrivals all lie in
-    // steps already run leave the table when it is rewritten); all-or-nothing (a batch that
-    // overflows a table changes nothing)
-    std::unordered_map<uint64_t, std::vector<Engine::XRec>> xnew;
-    std::unordered_map<uint64_t, std::vector<Engine::WRec>> wnew;   // the wide kernels' tables, by the same rules
-    for (size_t i = 0; e->wide_rec && i < staged.size(); ++i) {
-        const InjDev& r = staged[i];
-        const uint64_t dst[4] = {r.dst, r.dst_hi[0], r.dst_hi[1], r.dst_hi[2]};
-        const bool xsend = r.kind == BRC_INJ_SEND && (r.type & 2);
-        const bool xmsg = r.kind == BRC_INJ_MSG && r.restricted;
-        if ((!xsend && !xmsg) || !any4(dst)) continue;   // no link left: no record
-        const uint64_t item = staged_item[i];
-        if (!wnew.count(item)) {
-            std::vector<Engine::WRec> v0;
-            if (e->wrec.count(item))
-                for (const auto& q : e->wrec[item])
-                    if (!(its[item].initialized != 0 && q.t + c.delay_max < its[item].t)) v0.push_back(q);
-            wnew[item] = v0;
-        }
-        auto& v = wnew[item];
-        if (v.size() >= XSEND_MAX) {
-            e->err = "more than " + std::to_string(XSEND_MAX) + " extra-SEND / restricted ECHO / READY records in flight in one instance";
-            return BRC_E_UNSUPPORTED;
-        }
-        v.push_back(Engine::WRec{r.slot, r.t, xsend ? 0u : (uint32_t)r.type, r.node, {dst[0], dst[1], dst[2], dst[3]}});
-    }
-    for (size_t i = 0; !e->wide_rec && i < staged.size(); ++i) {
-        const InjDev& r = staged[i];
-        const bool xsend = r.kind == BRC_INJ_SEND && (r.type & 2);
-        const bool xmsg = r.kind == BRC_INJ_MSG && r.restricted && r.dst != 0;   // no link left: no record
-        if (!xsend && !xmsg) continue;
-        const uint32_t rtype = xmsg ? r.type : 0u;
-        const uint64_t item = staged_item[i];
-        if (!xnew.count(item)) {
-            // the table is rewritten: records whose arrivals all lie in steps already run are
-            // dropped, so the kernel's per-step scan covers live records only (xs_n shrinks)
-            std::vector<Engine::XRec> v0;
-            if (e->xrec.count(item))
-                for (const auto& q : e->xrec[item])
-                    if (!(its[item].initialized != 0 && q.t + c.delay_max < its[item].t)) v0.push_back(q);
-            xnew[item] = v0;
-        }
-        auto& v = xnew[item];
-        int slot = -1;
-        for (size_t j = 0; j < v.size(); ++j) {
-            if (v[j].k == r.slot && v[j].t == r.t && v[j].seg == r.seg && v[j].type == rtype && v[j].dst == r.dst &&
-                !((v[j].smask >> r.node) & 1ull)) {
-                slot = (int)j;
-                break;
-            }
-        }
-        const Engine::XRec nr = {r.slot, r.t, r.seg, rtype, 1ull << r.node, r.dst};
-        if (slot >= 0) v[slot].smask |= 1ull << r.node;
-        else if (v.size() < XSEND_MAX) v.push_back(nr);
-        else {
-            e->err = "more than " + std::to_string(XSEND_MAX) + " extra-SEND / restricted ECHO / READY records in flight in one item";
-            return BRC_E_UNSUPPORTED;
-        }
-    }
-    std::vector<uint64_t> xbuf;
-    xbuf.reserve(xnew.size() * (3 * XSEND_MAX + 1));
-    for (auto& kv : xnew) {
-        e->xrec[kv.first] = kv.second;
-        const size_t o = xbuf.size();
-        xbuf.resize(o + 3 * XSEND_MAX + 1, 0);
-        for (size_t j = 0; j < kv.second.size(); ++j) {
-            const auto& q = kv.second[j];
-            xbuf[o + 3 * j] = (uint64_t)q.k | ((uint64_t)q.t << 16) | ((uint64_t)q.seg << 40) | ((uint64_t)q.type << XS_TYPE_SH);
-            xbuf[o + 3 * j + 1] = q.smask;
-            xbuf[o + 3 * j + 2] = q.dst;
-        }
-        xbuf[o + 3 * XSEND_MAX] = kv.second.size();
-        HIPCHK(e, hipMemcpyAsync(e->xsend + kv.first * 3 * XSEND_MAX, &xbuf[o], 3 * XSEND_MAX * 8, hipMemcpyHostToDevice,
-                                 e->stream));
-        HIPCHK(e, hipMemcpyAsync(e->xsn + kv.first, &xbuf[o + 3 * XSEND_MAX], 4, hipMemcpyHostToDevice, e->stream));
-    }
-    std::vector<uint64_t> wbuf;
-    wbuf.reserve(wnew.size() * (WREC_W * XSEND_MAX + 1));
-    for (auto& kv : wnew) {
-        e->wrec[kv.first] = kv.second;
-        const size_t o = wbuf.size();
-        wbuf.resize(o + WREC_W * XSEND_MAX + 1, 0);
-        for (size_t j = 0; j < kv.second.size(); ++j) {
-            const auto& q = kv.second[j];
-            wbuf[o + WREC_W * j] = (uint64_t)q.k | ((uint64_t)q.t << 16) | ((uint64_t)q.type << XS_TYPE_SH) |
-                                   ((uint64_t)q.node << WREC_NODE_SH);
-            for (int w = 0; w < 4; ++w) wbuf[o + WREC_W * j + 1 + w] = q.dst[w];
-        }
-        wbuf[o + WREC_W * XSEND_MAX] = kv.second.size();
-        HIPCHK(e, hipMemcpyAsync(e->xsend + kv.first * WREC_W * XSEND_MAX, &wbuf[o], WREC_W * XSEND_MAX * 8,
-                                 hipMemcpyHostToDevice, e->stream));
-        HIPCHK(e, hipMemcpyAsync(e->xsn + kv.first, &wbuf[o + WREC_W * XSEND_MAX], 4, hipMemcpyHostToDevice, e->stream));
-    }
-    for (size_t i = 0; i < staged.size(); ++i) e->pending[staged_item[i]].push_back(staged[i]);
-    // the records that can allocate a key slot, for the generation budget (gen_used)
-    for (size_t i = 0; !(e->compact || e->wide) && i < staged.size(); ++i) {
-        const InjDev& r = staged[i];
-        const uint64_t in = staged_item[i] * e->ipw + r.seg;
-        if (r.kind == BRC_INJ_PROPOSE) {
-            e->gen_props = std::max<uint64_t>(e->gen_props, ++e->prop_recs[(in << 32) | r.node]);
-        } else if (r.kind == BRC_INJ_KEY || (r.kind == BRC_INJ_SEND && !(r.type & 2))) {
-            const uint32_t kp = r.slot / c.key_window;
-            const uint32_t nth = ++e->key_recs[(in << 32) | ((uint64_t)kp << 16) | r.s];
-            if (nth > 1 || c.protocol == BRC_PROTO_CONSENSUS)
-                e->gen_extra = std::max<uint64_t>(e->gen_extra, ++e->slot_extra[(in << 32) | r.slot]);
-        }
-    }
-    for (const auto& kv : new_wmsg) e->wmsg[kv.first] = kv.second;
-    for (const auto& kv : new_count) e->send_count[kv.first] += kv.second;
-    for (const auto& kv : new_used) e->msg_used[kv.first] |= kv.second;
-    for (const auto& kv : new_rec) e->msg_rec[kv.first] = true;
-    for (auto& kv : new_dst) {
-        auto& v = e->send_dst[kv.first];
-        v.insert(v.end(), kv.second.begin(), kv.second.end());
-    }
-    for (uint64_t in : reopen) {
-        ist[in].status = BRC_RUNNING;
-        HIPCHK(e, hipMemcpyAsync(&e->inst[in], &ist[in], sizeof(InstState), hipMemcpyHostToDevice, e->stream));
-    }
+    for (size_t i = 0; i < b.staged.size(); ++i) e->pending[b.staged_item[i]].push_back(b.staged[i]);
+    for (const auto& ro : b.reopen)
+        HIPCHK(e, hipMemcpyAsync(&e->inst[ro.first], &ro.second, sizeof(InstState), hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (count) e->inj_dirty = true;
+    e->book.commit(*e, e->cfg, b);
+    if (count) e->inj_dirty = true;   // (also when nothing was staged: a repeated SEND with no link left)
     return BRC_OK;
 }
 
@@ -843,32 +510,14 @@ int brc_run(void* h, uint32_t max_steps, uint32_t* running_left) {
         e->err = "proposals not loaded";
         return BRC_E_STATE;
     }
-    // slot generations are 13-bit tags: past the budget a stale cell could read as current.  brc_reset clears
-    // fully once gen_base + gen_cur reaches GEN_FULL_CLEAR, and so does the first run of an epoch whose staged
-    // records need it (nothing has run: every slot is free, only tags and stale cells are dropped), so gen_base
-    // stays below GEN_FULL_CLEAR and phase indices alone never get here (s_limit turns them into BRC_OVERFLOW).
-    // Injected records do: KEYs of one key allocate its slot once each, and nothing can clear an epoch under way.
-    // The lean (compact-cell) kernels, the wide kernels and the lifetime kernel keep no generation tags:
-    // a slot's row is rewritten at allocation, so only the 14-bit phase-index snapshot bounds them.
-    const uint64_t gen_hard = GEN_MASK - 2;
     const bool genfree = e->compact || e->wide;    // no cell generation tags (rows rewritten at allocation)
     // (a fresh engine has consumed no record: the upload below leaves `pending` as it is, and an engine that is
     // not fresh never takes the lifetime kernel)
     bool no_inj = true;
     for (const auto& v : e->pending) if (!v.empty()) { no_inj = false; break; }
     const bool life = e->life_cfg && e->fresh && no_inj && max_steps == 0 && !e->values_wide;
-    bool gen_clear = false;
-    if (!genfree && !life) {
-        gen_clear = e->fresh && e->gen_base > 0 && e->gen_base + gen_used(e) >= GEN_FULL_CLEAR;
-        if ((gen_clear ? 0 : e->gen_base) + gen_used(e) >= gen_hard) {
-            // gen_used counts a key's first record under BRB as its one allocation: on a fresh engine the 8188th KEY
-            // of one key (consensus protocol: the 8187th record of one slot) is the first to get here
-            e->err = "slot generation budget exhausted: call brc_reset (the records injected in this epoch can allocate "
-                     "one key slot more often than the " + std::to_string(gen_hard - 1 - (gen_clear ? 0 : e->gen_base)) +
-                     " generation tags left)";
-            return BRC_E_STATE;
-        }
-    }
+    bool gen_clear = false;                        // the slot generation budget (brc_inject.h run_budget)
+    if (!e->book.run_budget(c, e->fresh, genfree, life, &gen_clear, &e->err)) return BRC_E_STATE;
     int rc = upload_injections(e);
     if (rc) return rc;
     if (!life && !e->step_ok) { e->err = life_only_why(*e, true); return BRC_E_UNSUPPORTED; }
@@ -880,7 +529,7 @@ int brc_run(void* h, uint32_t max_steps, uint32_t* running_left) {
         rc = fill_cells(e);
         if (rc) return rc;
         HIPCHK(e, hipMemsetAsync(e->mgen, 0, e->mgen_bytes, e->stream));
-        e->gen_base = 0;
+        e->book.full_clear();   // (a fresh engine: gen_cur is 0 already)
     }
     Params P;
     memset(&P, 0, sizeof(P));
@@ -898,14 +547,7 @@ int brc_run(void* h, uint32_t max_steps, uint32_t* running_left) {
     P.nL = delay_values(c.delay_model, c.delay_max);
     P.event_cap = c.event_capacity;
     P.mode = c.mode; P.coin_seed = c.coin_seed;
-    // a slot allocated for phase index s has been reallocated at most gen_base + passes * (s / Q + 1) + gen_extra
-    // times (gen_used; the budget check above keeps the difference positive)
-    // (and phase indices stay below 2^14 - 1: the narrow kernel's consensus snapshot keeps s + 1 in 14 bits)
-    // (the lifetime kernel reads no s_limit; elsewhere the budget check above keeps the difference positive)
-    const uint64_t gen_spent = e->gen_base + e->gen_extra;
-    P.s_limit = (genfree || life || gen_spent + 1 >= gen_hard)
-                    ? 0x3FFEu
-                    : (uint32_t)std::min<uint64_t>(0x3FFEull, (gen_hard - 1 - gen_spent) / gen_passes(e) * c.key_window);
+    P.s_limit = e->book.s_limit(c, genfree, life);
     P.cells = e->cells; P.meta = e->meta; P.mgen = e->mgen; P.kdst = e->kdst;
     P.act = e->act; P.actany = e->actany; P.items = e->items;
     P.inst = e->inst; P.istats = e->istats; P.cons0 = e->cons0; P.cons1 = e->cons1; P.hmask = e->hmask;
@@ -927,10 +569,7 @@ int brc_run(void* h, uint32_t max_steps, uint32_t* running_left) {
     HIPCHK(e, hipEventElapsedTime(&e->last_ms, e->ev0, e->ev1));
     unsigned long long gc[8];
     HIPCHK(e, hipMemcpy(gc, e->gcount, sizeof(gc), hipMemcpyDeviceToHost));
-    if (!genfree && !life) {
-        e->gen_smax = std::max<uint64_t>(e->gen_smax, gc[5]);   // gc[5]: max phase index
-        e->gen_cur = std::max<uint64_t>(e->gen_cur, gen_used(e));
-    }
+    if (!genfree && !life) e->book.note_run(c, gc[5]);   // gc[5]: max phase index
     if (running_left) *running_left = (uint32_t)gc[6];   // counted by the step kernel
     return BRC_OK;
 }
@@ -939,22 +578,11 @@ int brc_reset(void* h) {
     Engine* e = static_cast<Engine*>(h);
     if (!e) return BRC_E_INVALID;
     HIPCHK(e, hipSetDevice(e->cfg.device));
-    const bool full = e->gen_base + e->gen_cur >= GEN_FULL_CLEAR;
-    if (!full) { e->gen_base += e->gen_cur; e->gen_cur = 0; }
-    int rc = clear_state(e, full);   // full: gen_base = gen_cur = 0
+    const bool full = e->book.close_epoch();
+    int rc = clear_state(e, full);   // full: book.full_clear()
     if (rc) return rc;
     for (auto& v : e->pending) v.clear();
-    e->send_count.clear();
-    e->send_dst.clear();
-    e->xrec.clear();
-    e->msg_used.clear();
-    e->msg_rec.clear();
-    e->gen_smax = e->gen_extra = e->gen_props = 0;
-    e->key_recs.clear();
-    e->slot_extra.clear();
-    e->prop_recs.clear();
-    e->wrec.clear();
-    e->wmsg.clear();
+    e->book.clear_epoch();
     if (e->pattern_active) {
         e->pattern_active = false;
         rc = apply_pattern(e);

@@ -11,7 +11,6 @@ namespace brc {
 constexpr uint32_t NEVER = 0xFFFFu;
 constexpr uint64_t TIMES_NEVER = 0xFFFFFFFF00000000ull;
 constexpr uint32_t F_EEX = 1, F_REX = 2, F_DEL = 4, F_ES = 8, F_RS = 16;
-constexpr uint32_t GEN_MASK = 0x1FFF;
 constexpr uint32_t GEN_RESTRICTED = 0x80000000u;
 constexpr uint32_t GEN16_RESTRICTED = 0x8000u;  // the narrow kernel's 16-bit LDS copy of mgen
 constexpr uint32_t GEN16_XDONE = 0x4000u;       // ... key processed by this step's extra-SEND pre-pass (brc_step.h)
@@ -21,7 +20,6 @@ __host__ __device__ inline uint16_t gen16(uint32_t g) {
 __host__ __device__ inline uint32_t gen32(uint16_t g) {
     return (g & GEN_MASK) | ((g & GEN16_RESTRICTED) ? GEN_RESTRICTED : 0u);
 }
-constexpr uint32_t GEN_FULL_CLEAR = 6000;   // host forces a full clear before tags can wrap
 // The consensus pass's deferred-SEND queue (brc_step.h, brc_life.h send_key): the SENDs one replica starts in
 // one step's pass -- one per phase end, consecutive phase indices -- at most SENDQ_MAX of them, else
 // BRC_OVERFLOW.  One bound for every kernel, so the step and key-lifetime kernels overflow at the same
@@ -44,20 +42,6 @@ template <uint32_t VB> struct SendQ {      // the queued SENDs' VB-bit value ids
         return (uint32_t)((i < 16 ? w[0] : w[VB == 2 ? 0 : 1]) >> (4 * (i & 15u))) & 15u;
     }
 };
-
-struct InjDev {       // 48 B, per item CSR, sorted by t
-    uint32_t t;
-    uint16_t slot, s;
-    uint8_t kind, type, seg, node;
-    int8_t value;
-    uint8_t restricted;   // SEND to a strict subset of the peers (set by the host for n > 64); MSG: bit 0 = an
-                          // ECHO / READY on the links node -> dst only (a record of the item's table lands it),
-                          // bit 1 = the first link (node, type, key) ever used: a SEND event (brc_step.h)
-    uint8_t pad[2];
-    uint64_t dst;         // destinations 0..63 (the narrow kernel reads the first 24 B only)
-    uint64_t dst_hi[3];   // destinations 64..255 (wide kernel)
-};
-
 
 // Compact cell of the lean kernels (NPAD = 64, sender peers: brc_step.h), one u32:
 //   bits 0-4 flags F_EEX, F_REX, F_DEL, F_ES, F_RS
@@ -99,12 +83,6 @@ struct Params {
     unsigned long long* gcount;   // [0] cell_steps [1] arrivals [2] msgs [3] deliveries [4] lane loads [5] max s
                                   // [6] instances still running after the launch
 };
-
-// an extra-SEND record's first word (XSEND_MAX, brc_layout.h): key slot | step << 16 | instance segment << 40 |
-// message type << XS_TYPE_SH (0: an extra SEND; BRC_ECHO / BRC_READY: a restricted message)
-constexpr uint32_t XS_TYPE_SH = 48;
-// ... on the wide kernels under BRC_FLAG_WIDE_RECORDS (WREC_W, brc_layout.h): the one sender
-constexpr uint32_t WREC_NODE_SH = 56;
 
 // Consensus record word 0 (cons0): round [0,16) | phase [16,20) | nvals [20,24) | order [24,48) (the
 // value ids in insertion order, 2 or 3 bits each) | value_count [48,64)

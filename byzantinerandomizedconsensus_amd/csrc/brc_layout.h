@@ -76,9 +76,33 @@ BRC_HD inline uint32_t delay_values(uint32_t model, uint32_t dmax) {
 constexpr uint32_t XSEND_MAX = 16;
 // Wide kernels under BRC_FLAG_WIDE_RECORDS (brc_step_wide.h REC): the same table per instance holds restricted
 // ECHO / READY records and extra SENDs (type 0: a SEND of a key SENT before), WREC_W words each -- the first word as
-// on the narrow kernels (brc_internal.h XS_TYPE_SH) with the one sender at WREC_NODE_SH (no segment: one instance per
+// on the narrow kernels (XS_TYPE_SH below) with the one sender at WREC_NODE_SH (no segment: one instance per
 // workgroup), then the destination set's four words (words past NPAD / 64 are zero)
 constexpr uint32_t WREC_W = 5;
+
+// Slot generation tags of the non-lean narrow step kernels (brc_internal.h gen16 / gen32): 13 bits; the host forces a
+// full clear before they can wrap (brc_inject.h InjectBook)
+constexpr uint32_t GEN_MASK = 0x1FFF;
+constexpr uint32_t GEN_FULL_CLEAR = 6000;
+
+struct InjDev {       // 48 B, per item CSR, sorted by t
+    uint32_t t;
+    uint16_t slot, s;
+    uint8_t kind, type, seg, node;
+    int8_t value;
+    uint8_t restricted;   // SEND to a strict subset of the peers (set by the host for n > 64); MSG: bit 0 = an
+                          // ECHO / READY on the links node -> dst only (a record of the item's table lands it),
+                          // bit 1 = the first link (node, type, key) ever used: a SEND event (brc_step.h)
+    uint8_t pad[2];
+    uint64_t dst;         // destinations 0..63 (the narrow kernel reads the first 24 B only)
+    uint64_t dst_hi[3];   // destinations 64..255 (wide kernel)
+};
+
+// an extra-SEND record's first word (XSEND_MAX): key slot | step << 16 | instance segment << 40 |
+// message type << XS_TYPE_SH (0: an extra SEND; BRC_ECHO / BRC_READY: a restricted message)
+constexpr uint32_t XS_TYPE_SH = 48;
+// ... on the wide kernels under BRC_FLAG_WIDE_RECORDS (WREC_W): the one sender
+constexpr uint32_t WREC_NODE_SH = 56;
 
 // Consensus value ids (core/byzantinerandomizedconsensus.py:57-60 keys its tables by payload string;
 // id 0 is str(NONE) == "-1"): 2 bits (3 strings + "-1") on the lean, wide and key-lifetime kernels,
